@@ -24,16 +24,24 @@ Multi-GPU: one process per GPU.  `python bench.py --gpus N` from a plain shell s
 never touches the GPU: it spawns N children with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_ADDR / MASTER_PORT set, waits,
 relays rank 0's JSON line and fails if any rank fails); under torchrun (`WORLD_SIZE` already set) the process IS a rank.
 
-Timing: pre-spin (untimed, until the clock is steady) -> barrier + synchronize -> W warm-up steps -> [event] K steps
-[event] -> K more steps without per-launch sampling (cross-check) -> the episode-end exchange, timed on its own ->
-synchronize + barrier.  `ms_per_step` = the event pair's device time / K (max over ranks) + allgather_ms / 1000 (one
-exchange per 1000-tick episode); nothing synchronises the host between the warm-up and the timed steps.
+Timing: pre-spin (untimed, until the clock is steady; the handles are then put back where its first 32-tick chunk left
+them) -> barrier + synchronize -> W warm-up steps -> [event] K steps [event] -> (--full: K more steps without per-launch
+sampling, the cross-check) -> the episode-end exchange, timed on its own -> synchronize + barrier.  `ms_per_step` = the
+event pair's device time / K (max over ranks) + allgather_ms / 1000 (one exchange per 1000-tick episode); nothing
+synchronises the host between the warm-up and the timed steps.  With the same arguments every run times the same ticks
+from the same synthetic inputs: 32 + W + K of them from the seeded states and candidates.
 
 One JSON line on stdout (rank 0).  `roofline` prices the dominant kernel: algorithmic bytes per launch
 / its mean duration over >= 20 launches of the timed region, from start / stop events carried by the dispatches
-themselves on the engine's own stream (mean, median, min reported; `kernel` is what rcg_last_launch says ran).  `parity` compares
-outputs of the same run's kernels with the CPU oracle.  `cpu_baseline` is the C oracle (oracle/oracle.c, kind "port")
-timed on this box's host cores on a bounded sample of the same workload.
+themselves on the engine's own stream (mean, median, min reported; `kernel` is what rcg_last_launch says ran).
+  --full              also runs what the headline does not need: `parity` (outputs of the same run's kernels against the
+                      CPU oracle), `secondary` (other regimes and the other element width: value_closed_loop,
+                      value_<width>), `cpu_baseline` (the C oracle, oracle/oracle.c, kind "port", and the reference
+                      algorithm, timed on the host cores this job owns on a bounded sample of the same workload) and the
+                      cross-check above; --no-parity / --no-secondary / --no-cpu-baseline leave parts of it out.
+  --dump-outputs DIR  writes what the last timed step left a caller (state, action, best_J, best_idx, accum; the critic
+                      weights in the critic modes) as DIR/<name>.npy, one row per env, at most 64 MB in all (above that, a
+                      fixed seeded sample of envs).
 """
 import argparse
 import json
@@ -52,6 +60,7 @@ PRESPIN_S = 0.35    # untimed clock pre-spin: the first launches after the GPU w
 PRESPIN_MAX_S = 3.0
 C4_TOTAL_ENVS = 524288
 EPISODE_TICKS = 1000  # T = 1 000 control ticks per episode (10 s at the preset's t1); one exchange per episode
+PRESPIN_KEPT = 32     # pre-spin ticks the handles keep: the spin's first chunk (main(): the handles are put back behind it)
 
 
 def parse(argv=None):
@@ -71,6 +80,13 @@ def parse(argv=None):
                    help="element type of the headline tick.  Default f64 = the reference's own arithmetic width for the streamed "
                         "(HBM-bound) configs, with the f32 tick (half the candidate bytes) beside it as value_f32 / roofline_f32; "
                         "the generated-grid regime (--regime generated, --config C5) is a float32 regime (k_ticks_pk) and defaults to f32")
+    p.add_argument("--full", action="store_true",
+                   help="also measure and check what the headline does not need: the parity check against the CPU oracle, the "
+                        "secondary regimes, the CPU baselines and the unsampled cross-check of the K steps (the --no-* "
+                        "switches below thin this out)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last of them left a caller (state, action, best_J, best_idx, "
+                        "accum, critic weights where the mode has them) as DIR/<name>.npy, at most 64 MB in all")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-secondary", action="store_true")
     p.add_argument("--no-parity", action="store_true")
@@ -114,6 +130,8 @@ def parse(argv=None):
         p.error("--parts applies to the single-system configs (C5 already runs one handle per system type)")
     if a.config == "C5" and a.regime != "generated":
         p.error("--config C5 is the generated-candidate workload (BASELINE configs[4]: 256-candidate grid search)")
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
 
 
@@ -501,6 +519,85 @@ def pool_states(rng, name, n):
     return np.stack([rng.uniform(0, 2, n), rng.uniform(-2, 2, n)], axis=-1)
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# handle fields copied on the device: stream-ordered copies on each handle's own stream (rcg_get_field / rcg_set_field with
+# RCG_DEVICE), so nothing here makes the host wait or lets the queue run dry
+# ---------------------------------------------------------------------------------------------------------------
+# what a caller of the tick reads back: name in --dump-outputs -> field
+OUTPUT_FIELDS = (("state", "FIELD_STATE"), ("action", "FIELD_ACTION"), ("best_J", "FIELD_BEST_J"),
+                 ("best_idx", "FIELD_BEST_IDX"), ("accum", "FIELD_ACCUM"), ("w_critic", "FIELD_W_CRITIC"))
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def field_buffers(engines, torch, fields=None):
+    """Per handle, one device buffer for each of ``fields`` it has allocated (None: every field, a whole snapshot as
+    Engine.state_dict takes it)."""
+    from rcognita_amd import _native as N
+
+    L = N.lib()
+    fields = range(N.FIELD_COUNT) if fields is None else fields
+    return [{f: torch.empty(int(L.rcg_field_bytes(e._h, f)), dtype=torch.uint8, device="cuda")
+             for f in fields if L.rcg_field_bytes(e._h, f) > 0} for e in engines]
+
+
+def fields_take(engines, bufs):
+    """Enqueue the copies of the handles' fields into ``bufs``; returns their tick counters."""
+    from rcognita_amd import _native as N
+
+    for e, b in zip(engines, bufs):
+        for f, t in b.items():
+            N.check(N.lib().rcg_get_field(e._h, f, t.data_ptr(), N.DEVICE), e._h)
+    return [int(N.lib().rcg_tick_count(e._h)) for e in engines]
+
+
+def fields_restore(engines, bufs, ticks):
+    """Put the handles back where fields_take(every field) found them, as Engine.load_state_dict does: STATE first
+    (rcg_set_field(STATE) also writes STATE_PREV, which is then restored from its own copy), the other fields, the tick
+    counter."""
+    from rcognita_amd import _native as N
+
+    for e, b, n in zip(engines, bufs, ticks):
+        for f in sorted(b, key=lambda f: f != N.FIELD_STATE):
+            N.check(N.lib().rcg_set_field(e._h, f, b[f].data_ptr(), N.DEVICE), e._h)
+        N.check(N.lib().rcg_set_tick_count(e._h, n), e._h)
+
+
+def write_outputs(dirname, engines, bufs):
+    """--dump-outputs: the fields copied right behind the last timed step -> DIR/<name>.npy, one row per env, floating
+    fields in the run's element width, integer fields as float64 (several handles: names prefixed handle<i>_).  Above
+    DUMP_LIMIT_BYTES the same fixed, seeded sample of envs is taken from every array of a handle, and its env indices are
+    written beside them (<prefix>env_index.npy).  Returns {name: shape}."""
+    import numpy as np
+
+    from rcognita_amd import _native as N
+
+    names = {getattr(N, a): n for n, a in OUTPUT_FIELDS}
+    per_handle = []
+    for i, (e, b) in enumerate(zip(engines, bufs)):
+        pre = "" if len(engines) == 1 else f"handle{i}_"
+        arrs = {}
+        for f, t in b.items():
+            shape, dt, _, d2h = e._field_meta(f)
+            a = np.ascontiguousarray(d2h(t.cpu().numpy().view(dt).reshape(shape)))
+            arrs[pre + names[f]] = a if np.issubdtype(a.dtype, np.floating) else a.astype(np.float64)
+        per_handle.append((pre, e.B, arrs))
+    total = sum(a.nbytes for _, _, arrs in per_handle for a in arrs.values())
+    frac = 1.0
+    if total > DUMP_LIMIT_BYTES:  # the env indices written beside a sample count against the limit too
+        frac = DUMP_LIMIT_BYTES / (total + 8 * sum(B for _, B, _ in per_handle))
+    os.makedirs(dirname, exist_ok=True)
+    written = {}
+    for i, (pre, B, arrs) in enumerate(per_handle):
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(i).choice(B, int(B * frac), replace=False))
+            arrs = {k: a[idx] for k, a in arrs.items()}
+            arrs[pre + "env_index"] = idx.astype(np.float64)
+        for k, a in arrs.items():
+            np.save(os.path.join(dirname, k + ".npy"), a)
+            written[k] = list(a.shape)
+    return written
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -686,22 +783,31 @@ def main(argv=None):
                 main_stream.wait_stream(st)
         dist.all_gather(gathered, returns_dev if coll_dev.type == "cuda" else returns_dev.cpu())
 
+    # the handles as they stand after the first pre-spin chunk, and (--dump-outputs) what the last timed step leaves a caller
+    snap_bufs = field_buffers(engines, torch)
+    dump = args.dump_outputs is not None and rank == 0
+    out_bufs = field_buffers(engines, torch, [getattr(N, a) for _, a in OUTPUT_FIELDS]) if dump else None
     if dist is not None:
         exchange_returns()  # untimed: RCCL builds its rings / channels on the first collective of each kind
-        torch.cuda.synchronize()
+    torch.cuda.synchronize()
 
     # ---- untimed: clock pre-spin (>= PRESPIN_S of the same kernels) ----------------------------------------------------
     # The GPU reaches its steady clock after ~100 ticks (20 ms) of CONTINUOUS work and falls back within 10 ms of idling
     # (tools/clock_ramp.py), so the spin never lets the queue run dry: the host waits on the events recorded two chunks
-    # ago (on the engines' own streams).
+    # ago (on the engines' own streams).  How many chunks that takes depends on the clock, so the handles are copied
+    # behind the first chunk and put back at the end of the spin: whatever it took, the timed path is the same PRESPIN_KEPT
+    # + W + K ticks from the same inputs (--dump-outputs compares runs and builds output for output).
     prespin = 0
     t_spin = time.perf_counter()
     evs, chunk_ms = [], []
+    snap_ticks = None
     while True:
         for _ in range(32):
             tick()
         prespin += 32
         evs.append(record_all())
+        if snap_ticks is None:
+            snap_ticks = fields_take(engines, snap_bufs)
         if len(evs) >= 4:
             for ev in evs[-3]:
                 ev.synchronize()  # two chunks stay queued behind it: the GPU never runs dry
@@ -713,6 +819,7 @@ def main(argv=None):
             steady = len(last) == 4 and (max(last) - min(last)) <= 0.015 * min(last)
             if (spun >= PRESPIN_S and steady) or spun >= PRESPIN_MAX_S:
                 break
+    fields_restore(engines, snap_bufs, snap_ticks)  # in-stream, behind the spin's last chunk: the queue does not run dry
 
     # ---- the contract's bracket: barrier + synchronize, W untimed warm-up steps, then EXACTLY K timed steps between two
     # in-stream events (no host synchronisation in between: the timed steps run in the flow the warm-up steps started),
@@ -738,12 +845,16 @@ def main(argv=None):
     ev_stop = record_all()
     for e in engines:
         e.profile_pause()
-    # the same K steps again without any per-launch event: what the sampling itself costs the stream
-    align_streams()
-    ev_start2 = record_all()
-    for _ in range(args.steps):
-        tick()
-    ev_stop2 = record_all()
+    if dump:  # in-stream copies behind the last timed step (the events above have joined any split tick)
+        fields_take(engines, out_bufs)
+    crosscheck = args.steps if args.full else 0
+    if crosscheck:
+        # the same K steps again without any per-launch event: what the sampling itself costs the stream
+        align_streams()
+        ev_start2 = record_all()
+        for _ in range(crosscheck):
+            tick()
+        ev_stop2 = record_all()
     # the episode-end exchange, timed on its own: the design makes ONE exchange per episode (EPISODE_TICKS control ticks),
     # so its cost enters a step as allgather_ms / EPISODE_TICKS - not once per K steps of a short run
     n_exch = 5 if dist is not None else 0
@@ -759,7 +870,7 @@ def main(argv=None):
     barrier()
     wall_s = time.perf_counter() - t_wall0
     compute_ms = span_ms(ev_start, ev_stop)
-    unbracketed_ms = span_ms(ev_start2, ev_stop2)
+    unbracketed_ms = span_ms(ev_start2, ev_stop2) if crosscheck else 0.0
     allgather_ms = (ex_a.elapsed_time(ex_b) / n_exch) if n_exch else 0.0
     if dist is not None:  # MAX over ranks (device times of each rank's own stream)
         tmax = torch.tensor([compute_ms, unbracketed_ms, allgather_ms], device=coll_dev, dtype=torch.float64)
@@ -779,7 +890,7 @@ def main(argv=None):
 
     summ = merge_summaries([e.episode_stats(from_accum=True)[0] for e in engines])
     total = gather_summaries(summ, dist, device=coll_dev, force=args.force_dist)  # per-shard summaries -> whole job
-    ticks_done = prespin + args.warmup + 2 * args.steps
+    ticks_done = PRESPIN_KEPT + args.warmup + args.steps + crosscheck
     for e in engines:
         steps_idx = e.get_field(N.FIELD_STEP_IDX)
         assert int(steps_idx.min()) == int(steps_idx.max()) == ticks_done, "step counter mismatch"
@@ -897,6 +1008,7 @@ def main(argv=None):
                    "handles_per_gpu": len(engines), "envs_per_handle": [e.B for e in engines],
                    "candidates": K, "nactor": Nh, "regime": args.regime, "parallelism": f"env-shard x{world}",
                    "actor_cost_evals_per_s": value * K, "prespin_ticks_untimed": prespin,
+                   "prespin_ticks_kept": PRESPIN_KEPT,
                    "prespin_last_chunks_ms_per_tick": [round(c / 32, 5) for c in chunk_ms[-4:]]},
         # how `value` was timed: K steps between two in-stream events (max over ranks), no host synchronisation between
         # the W warm-up steps and the K timed steps; the episode-end exchange enters per episode, not per K steps
@@ -907,11 +1019,12 @@ def main(argv=None):
                    "allgather_ms": allgather_ms if dist is not None else None,
                    "episode_ticks": EPISODE_TICKS,
                    "allgather_ms_per_step": (allgather_ms / EPISODE_TICKS) if dist is not None else None,
-                   "unbracketed_ms_per_step": unbracketed_ms / args.steps,
-                   "wall_ms_per_step_incl_warmup_and_crosscheck": wall_s * 1e3 / (args.warmup + 2 * args.steps),
-                   "note": "unbracketed = the same K steps repeated right behind the timed ones with no per-launch event "
-                           "(the sampling costs the stream ~7 us per sampled launch); wall = host clock from the barrier "
-                           "in front of the warm-up to the barrier behind everything, over all W + 2K steps (+ exchanges)"},
+                   "unbracketed_ms_per_step": (unbracketed_ms / crosscheck) if crosscheck else None,
+                   "wall_ms_per_step_incl_warmup_and_crosscheck": wall_s * 1e3 / (args.warmup + args.steps + crosscheck),
+                   "note": "unbracketed (--full) = the same K steps repeated right behind the timed ones with no per-launch "
+                           "event (the sampling costs the stream ~7 us per sampled launch); wall = host clock from the barrier "
+                           "in front of the warm-up to the barrier behind everything, over all W + K steps (+ K with --full) "
+                           "(+ exchanges)"},
         "rccl_ranks": (dist.get_world_size() if dist is not None else 1),
         "dist_backend": (args.dist_backend if dist is not None else None),
         "launcher": launcher,
@@ -976,11 +1089,17 @@ def main(argv=None):
                                          "4-cycle wave64 issue model tops out at 3.9e13)",
                                "hbm_frac_for_completeness": hbm["frac"]}
 
-    if not args.no_parity:
+    if dump:  # (the copies behind the last timed step finished before the barrier above)
+        out["outputs"] = {"dir": args.dump_outputs, "envs": "rank 0's" if world > 1 else "all",
+                          "after_ticks": ticks_done - crosscheck,
+                          "arrays": write_outputs(args.dump_outputs, engines, out_bufs)}
+
+    # ---- --full: everything the headline does not need, each on fresh handles or on the host ---------------------------
+    if args.full and not args.no_parity:
         out["parity"] = (parity_check_pool(args, local_rank, stream_ptr, K) if args.config == "C5" else
                          parity_check(args, local_rank, stream_ptr, x0, cand, K))
 
-    if not args.no_secondary and world == 1 and args.config == "C2":
+    if args.full and not args.no_secondary and world == 1 and args.config == "C2":
         out["secondary"] = secondary(args, local_rank, stream_ptr, x0, B, K, Nh, torch, Engine, N)
         if streamed and args.parts == 1 and Nh * 2 <= 40:
             try:
@@ -1004,7 +1123,7 @@ def main(argv=None):
                                               note=f"the same tick with {ow['dtype']} storage and arithmetic, this run "
                                                    "(secondary.other_width)")
 
-    if not args.no_cpu_baseline and world == 1 and args.config == "C2":
+    if args.full and not args.no_cpu_baseline and world == 1 and args.config == "C2":
         out["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
         out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
         try:

@@ -87,7 +87,7 @@ def test_rccl_world1_device_all_gather_of_returns_and_summary():
 
 def _bench(extra, timeout=900):
     cmd = [sys.executable, BENCH, "--steps", "6", "--warmup", "2", "--batch", "8192", "--candidates", "64",
-           "--no-cpu-baseline", "--no-secondary"] + extra
+           "--full", "--no-cpu-baseline", "--no-secondary"] + extra
     return subprocess.run(cmd, capture_output=True, text=True, timeout=timeout, env=_env())
 
 

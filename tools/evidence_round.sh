@@ -8,11 +8,11 @@ R=${1:-r03}
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 O=gpurun_out/ev_${R}
 mkdir -p "$O"
-B="--no-cpu-baseline --no-secondary"
+B="--full --no-cpu-baseline --no-secondary"
 PART=${PART:-all}   # a gpurun call lasts at most 1200 s: PART=1 bench lines, PART=2 sweeps / probes / test output
 if [ "$PART" != 2 ]; then
 # the driver's form, three consecutive runs (default flags otherwise: CPU baseline and secondary regimes included in the first)
-python bench.py --gpus 1 --steps 20 --warmup 5 > "$O/${R}_driver_form_1.json" 2> "$O/err.log"
+python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$O/${R}_driver_form_1.json" 2> "$O/err.log"
 python bench.py --gpus 1 --steps 20 --warmup 5 $B > "$O/${R}_driver_form_2.json" 2>> "$O/err.log"
 python bench.py --gpus 1 --steps 20 --warmup 5 $B > "$O/${R}_driver_form_3.json" 2>> "$O/err.log"
 # RCCL at world size 1; two ranks over gloo on the one GPU (functional: the N > 1 code path)

@@ -1,6 +1,8 @@
 #!/bin/bash
 # NOTE (round 6): bench.py's default element type is now f64 (the reference's width); this script was written for the f32 default of
 # rounds 1-5 - pass --dtype f32 where it says nothing, or use tools/profile_round6.sh, which produced profiles/r06_*.
+# NOTE: a bench.py run without --full prints the headline only; the parity check, the secondary regimes and the CPU
+# baselines these bench lines were recorded with need --full.
 # Reproduce the evidence kept under profiles/ for one round, on a GPU box (run through gpurun from the repo root):
 #
 #   gpurun --timeout 1200 -- 'bash tools/profile_round.sh r03'

@@ -9,12 +9,14 @@
 #       --write gpurun_out/prof_write_f32 --key k_actor_streamed_3wrobot_B65536_K256_N10_f32
 # The headline of bench.py is the float64 tick since round 6 (the reference's arithmetic width); the program itself follows `--`
 # (no env / bash -c hop under rocprofv3), counters in passes of their own (MI355X_MICROARCH.md, HBM / rocprofv3 section).
+# NOTE: a bench.py run without --full prints the headline only; the parity check, the secondary regimes and the CPU
+# baselines these bench lines were recorded with need --full (the $B lines below carry it).
 set -u
 PART=${PART:-1}
 cd /tmp && export TMPDIR=/tmp
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
-B="--no-cpu-baseline --no-secondary"
+B="--full --no-cpu-baseline --no-secondary"
 if [ "$PART" = 1 ]; then
 python bench.py > gpurun_out/bench_r06.json 2> gpurun_out/bench_r06.err
 for dt in f64 f32; do
