@@ -17,10 +17,12 @@ LIBDIR  := $(ROOT)rcognita_amd/lib
 OBJDIR  := $(ROOT)build/obj
 ORACLE  := $(ROOT)oracle
 
+GENDIR  := $(ROOT)build/gen
 HIPFLAGS := -O3 -std=c++17 --offload-arch=$(ARCH) -fPIC -Wall -Wno-unused-function -ffp-contract=fast \
-            -I$(ROOT)include -MMD -MP
-# the C ABI; the system-templated launchers and kernels: rcg_sys_inst.hip compiled once per (system, part), see that file
-UNITS   := rcg_api
+            -I$(ROOT)include -I$(GENDIR) -MMD -MP
+# the C ABI; systems registered at run time (hipRTC); the system-templated launchers and kernels: rcg_sys_inst.hip compiled
+# once per (system, part), see that file
+UNITS   := rcg_api rcg_rtc
 SYSP    := $(foreach s,Sys3WRobot.kVt3WRobot Sys3WRobotNI.kVt3WRobotNI Sys2Tank.kVt2Tank,$(foreach p,0 1 2 3 4,$(s).$(p)))
 SYSFLAGS = -DRCG_SYS=$(word 1,$(subst ., ,$*)) -DRCG_SYS_VT=$(word 2,$(subst ., ,$*)) -DRCG_SYS_PART=$(word 3,$(subst ., ,$*))
 # k_actor_dma instances: rcg_dma_inst.hip compiled once per (system, element type, group), see that file
@@ -35,6 +37,13 @@ OBJS    := $(call objs,$(OBJDIR))
 ALLHDRS := $(wildcard $(CSRC)/*.hpp) $(ROOT)include/rcg.h
 hdrs     = $(if $(wildcard $(1:.o=.d)),,$(ALLHDRS))
 .SECONDEXPANSION:
+
+# the kernel headers a runtime-compiled system needs, as string literals for rcg_rtc.hip (comments stripped)
+RTCHDRS := $(ROOT)include/rcg.h $(addprefix $(CSRC)/,rcg_math.hpp rcg_systems.hpp rcg_kernels.hpp rcg_loop.hpp rcg_actor_opt.hpp \
+           rcg_actor_dma.hpp rcg_actor_dma_packed.hpp)
+$(GENDIR)/rcg_rtc_headers.inc: $(RTCHDRS) $(ROOT)tools/embed_rtc_headers.py
+	@mkdir -p $(GENDIR)
+	python3 $(ROOT)tools/embed_rtc_headers.py $@ $(RTCHDRS)
 
 DEVOBJDIR := $(ROOT)build/obj_dev
 DEVOBJS   := $(call objs,$(DEVOBJDIR))
@@ -62,7 +71,7 @@ $(OBJDIR)/%.o: $(CSRC)/%.hip $$(call hdrs,$$@)
 
 $(LIBDIR)/librcg.so: $(OBJS)
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(OBJS) -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(OBJS) -o $@ -lhiprtc
 
 $(ORACLE)/_build/liboracle.so: $(ORACLE)/oracle.c
 	@mkdir -p $(ORACLE)/_build
@@ -84,7 +93,7 @@ $(DEVOBJDIR)/%.o: $(CSRC)/%.hip $$(call hdrs,$$@)
 
 $(LIBDIR)/librcg_dev.so: $(DEVOBJS)
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(DEVOBJS) -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(DEVOBJS) -o $@ -lhiprtc
 
 # A/B build for tools/ab_lib.py: the same sources with extra defines (`make ab ABFLAGS="-DRCG_AB_..."`), linked as
 # rcognita_amd/lib/librcg_ab.so; never loaded by the package (a tool binds it with _native.use_library)
@@ -105,13 +114,13 @@ $(ABOBJDIR)/%.o: $(CSRC)/%.hip $$(call hdrs,$$@)
 
 $(LIBDIR)/librcg_ab.so: $(ABOBJS)
 	@mkdir -p $(LIBDIR)
-	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(ABOBJS) -o $@
+	$(HIPCC) --offload-arch=$(ARCH) -shared -fPIC -Wl,--no-undefined $(ABOBJS) -o $@ -lhiprtc
 
 # Sanitizer build (CPU only: GPU AddressSanitizer is not available on this pool).  --offload-host-only compiles the
 # host side of every .hip unit - the C ABI, argument checks, launch-geometry arithmetic - and drops the device code.
 asan: $(ASANDIR)/abi_asan
 ASANHIP := -std=c++17 --offload-arch=$(ARCH) --offload-host-only $(SANFLAGS) -fPIC -Wall -Wno-unused-function \
-           -ffp-contract=fast -I$(ROOT)include
+           -ffp-contract=fast -I$(ROOT)include -I$(GENDIR)
 
 $(ASANDIR)/rcg_dma.%.o: $(CSRC)/rcg_dma_inst.hip $$(call hdrs,$$@)
 	@mkdir -p $(ASANDIR)
@@ -137,10 +146,13 @@ $(ASANDIR)/no_device_image.c: $(ASANOBJS)
 
 $(ASANDIR)/abi_asan: $(ASANOBJS) $(ASANDIR)/asan_driver.o $(ASANDIR)/no_device_image.c
 	$(HOSTCLANG) -c $(ASANDIR)/no_device_image.c -o $(ASANDIR)/no_device_image.o
-	$(HIPCC) $(SANFLAGS) $(ASANOBJS) $(ASANDIR)/asan_driver.o $(ASANDIR)/no_device_image.o -o $@ -lm
+	$(HIPCC) $(SANFLAGS) $(ASANOBJS) $(ASANDIR)/asan_driver.o $(ASANDIR)/no_device_image.o -o $@ -lm -lhiprtc
+
+# (rcg_rtc.hip includes the generated header file)
+$(OBJDIR)/rcg_rtc.o $(DEVOBJDIR)/rcg_rtc.o $(ABOBJDIR)/rcg_rtc.o $(ASANDIR)/rcg_rtc.o: $(GENDIR)/rcg_rtc_headers.inc
 
 clean:
-	rm -rf $(LIBDIR)/librcg.so $(LIBDIR)/librcg_dev.so $(LIBDIR)/librcg_ab.so $(OBJDIR) $(DEVOBJDIR) $(ABOBJDIR) $(ASANDIR) $(ORACLE)/_build
+	rm -rf $(LIBDIR)/librcg.so $(LIBDIR)/librcg_dev.so $(LIBDIR)/librcg_ab.so $(OBJDIR) $(DEVOBJDIR) $(ABOBJDIR) $(ASANDIR) $(GENDIR) $(ORACLE)/_build
 
 # (the included dependency files are not targets: without this rule make tries to REMAKE them through its built-in
 # "link an executable from a .o" rule and compiles rcg_sys.*.d.o objects)

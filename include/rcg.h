@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 119 /* 117 + rcg_loop_step (_begin / _end), rcg_set_optimizer_tol (round 6) */
+#define RCG_VERSION 120 /* 119 + rcg_register_system, rcg_rtc_version, rcg_system_info (systems compiled at run time) */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -52,6 +52,8 @@ typedef enum rcg_status {
 
 /* rcognita/systems.py:255 (Sys3WRobot), :353 (Sys3WRobotNI), :401 (Sys2Tank) */
 typedef enum rcg_system { RCG_SYS_3WROBOT = 0, RCG_SYS_3WROBOT_NI = 1, RCG_SYS_2TANK = 2 } rcg_system;
+/* ids of the systems registered at run time (rcg_register_system) start here; 3 .. 15 are not ids */
+#define RCG_SYS_USER_BASE 16
 /* CtrlOptPred modes, rcognita/controllers.py:1304-1326 */
 typedef enum rcg_mode { RCG_MODE_MPC = 0, RCG_MODE_RQL = 1, RCG_MODE_SQL = 2 } rcg_mode;
 /* stage_obj_struct, rcognita/controllers.py:1076-1082 */
@@ -173,6 +175,25 @@ int rcg_version(void);
 const char* rcg_last_error(const rcg_handle* h);
 /* Number of visible HIP devices (0 if none / no driver).  Does not create a context. */
 int rcg_device_count(void);
+
+/* A system of your own, compiled at run time for gfx950 (hipRTC) against the library's kernel headers.  `policy_src` is a
+ * complete `struct <name> { ... };` in the shape of the built-ins ("Systems registered at run time"): DS, DU, NP,
+ * template <typename real> struct Pre, prepare, rhs<real, HW>; optional jac_T (enables rcg_actor_optimize /
+ * rcg_control_tick_opt), TGT, ZW_PRESET, SHARED_U1 (defaults false, 0, 0).  It may use rcg_math.hpp (sincos_sel, fma_r, ...) and
+ * the device math library.  The declared ds / du / np must match the struct (RCG_ERR_BAD_ARG otherwise) and stay within
+ * RCG_MAX_DS / RCG_MAX_DU / RCG_MAX_PARS (RCG_ERR_UNSUPPORTED otherwise).  Compiles the f32 and f64 programs before it returns
+ * (seconds; no device needed); a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error(NULL).  The same name and
+ * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
+ * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
+ * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  rcg_create
+ * refuses RQL / SQL and RCG_FLAG_DISTURB; the critic operators, the nominal controllers, rcg_actor_search,
+ * rcg_control_ticks and rcg_loop_step return RCG_ERR_UNSUPPORTED with the handle untouched. */
+int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
+/* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
+int rcg_rtc_version(int32_t* major, int32_t* minor);
+/* dimensions of a built-in or registered system, and whether it has the optimiser (jac_T; every built-in one has);
+ * any pointer may be NULL.  RCG_ERR_BAD_ARG for an id that names no system. */
+int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32_t* has_jac);
 
 /* ---- life cycle: System.__init__ (systems.py:69-145), Simulator.__init__ (simulator.py:71-154),
  *      CtrlOptPred.__init__ (controllers.py:811-1044) ------------------------------------------ */

@@ -67,6 +67,18 @@ class CtrlOptPred:
                 "sys_rhs must be the bound `_state_dyn` of a rcognita_amd System: arbitrary Python models cannot "
                 "run on the native path and there is no CPU fallback")
         self.sys = sys_obj
+        # a system compiled at run time (System.hip_policy) runs MPC: no critic kernels, no device search, the optimiser only
+        # when the policy has jac_T
+        info = type(sys_obj)._hip_info if type(sys_obj).hip_policy is not None else None
+        self._runtime_sys = info is not None
+        if info is not None:
+            if mode != "MPC":
+                raise NotImplementedError(f"{type(sys_obj).__name__} is compiled from hip_policy: mode {mode!r} needs the critic "
+                                          "kernels, which exist for the built-in systems only; use mode='MPC'")
+            if candidates is None and (actor_opt == "sampling" or not info["has_jac"]):
+                raise NotImplementedError(
+                    f"{type(sys_obj).__name__} is compiled from hip_policy: the device search (actor_opt='sampling') is not "
+                    "available for it, and the on-device optimiser needs jac_T in the policy; pass candidates=")
         self.dim_input, self.dim_output = dim_input, dim_output
         self.mode = mode
         self.ctrl_clock = t0
@@ -184,7 +196,7 @@ class CtrlOptPred:
         if hit is not None and hit[0]() is sim and hit[1] == key:  # (a weak reference: an id() may be reused by a later object)
             return hit[2]
         row = self.dim_output + self.dim_input + 2 + (self.dim_critic if self.mode != "MPC" else 0)
-        ok = (sim.sys is self.sys and sim.B == self.B and sim.dtype == self._dtype and not sim.is_disturb
+        ok = (not self._runtime_sys and sim.sys is self.sys and sim.B == self.B and sim.dtype == self._dtype and not sim.is_disturb
               and self.candidates is None and self._use_gradient and (self.mode == "MPC" or self.Ncritic - 1 >= 1)
               and self.B * (row + self.dim_input) * 8 <= 16384)
         import weakref

@@ -499,9 +499,11 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 // DMA_MPC_GENF; group 7: DMA_RQL_GEN_0 .. + 3.
 // Returns false when there is no instance for (row length r, variant).  ev_a / ev_b (both or neither): the launch carries
 // them as its start / stop events (rcg_profile, rcg_handle.hpp::ProfScope).
+#if !defined(__HIPCC_RTC__)  // (host code: not part of a runtime-compiled program, rcg_rtc.hip)
 template <typename Sys, typename real, int GROUP>
 bool launch_dma(int r, int variant, dim3 grid, dim3 block, size_t lds, hipStream_t s, const ActorArgs<real>& A,
                 const KParams<real>& P, hipEvent_t ev_a, hipEvent_t ev_b);
+#endif
 
 // longest row with an instance, in reals: 40 = the robots' Nactor = 20 (f32: 160 bytes; f64: 320 bytes, a block's four
 // tiles are then 80 KB of LDS - beyond the default dynamic limit, launch_dma raises it for those instances)

@@ -363,8 +363,10 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
 }
 
 // instances: rcg_dma_inst.hip, groups 3 (MPC), 4 (SQL), 5 (RQL) - one object per system x element type x group
+#if !defined(__HIPCC_RTC__)  // (host code: not part of a runtime-compiled program, rcg_rtc.hip)
 template <typename Sys, typename real, int GROUP>
 bool launch_dma_packed(int r, int variant, dim3 grid, dim3 block, size_t lds, hipStream_t s, const ActorArgs<real>& A,
                        const KParams<real>& P, hipEvent_t ev_a, hipEvent_t ev_b);
+#endif
 
 }  // namespace rcg

@@ -28,6 +28,8 @@ int rcg_fail(rcg_handle* h, int code, const char* fmt, ...) {
   return code;
 }
 
+void rcg_set_thread_error(const std::string& text) { g_err = text; }
+
 // Turn the pending event pairs into totals and samples.  Returns RCG_OK, or RCG_ERR_HIP (text in the handle) when a
 // pair could not be read - e.g. one that no dispatch ever recorded: the readers pass that on instead of returning
 // totals that silently miss launches.
@@ -173,6 +175,19 @@ int rcg_version(void) { return RCG_VERSION; }
 
 const char* rcg_last_error(const rcg_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
+int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32_t* has_jac) {
+  RtcDims d{0, 0, 0, true};
+  if (sys_id >= 0 && sys_id <= 2)
+    d = RtcDims{kDims[sys_id][0], kDims[sys_id][1], kDims[sys_id][2], true};
+  else if (!(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_info: bad sys_id %d", sys_id);
+  if (ds) *ds = d.ds;
+  if (du) *du = d.du;
+  if (np) *np = d.np;
+  if (has_jac) *has_jac = d.has_jac ? 1 : 0;
+  return RCG_OK;
+}
+
 int rcg_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -185,7 +200,11 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   if (cfg->struct_size != (int32_t)sizeof(rcg_cfg))
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: struct_size %d != sizeof(rcg_cfg) %zu (ABI mismatch)",
                     cfg->struct_size, sizeof(rcg_cfg));
-  if (cfg->sys_id < 0 || cfg->sys_id > 2) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad sys_id %d", cfg->sys_id);
+  // a built-in system, or one registered at run time (rcg_rtc.hip: its dimensions come from the registry)
+  RtcDims rd{0, 0, 0, false};
+  const RtcSystem* rtc = cfg->sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(cfg->sys_id, &rd) : nullptr;
+  if ((cfg->sys_id < 0 || cfg->sys_id > 2) && !rtc)
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad sys_id %d", cfg->sys_id);
   if (cfg->batch < 1) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: batch must be >= 1");
   if (cfg->dtype != RCG_F32 && cfg->dtype != RCG_F64) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad dtype");
   if (cfg->mode < 0 || cfg->mode > 2) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad mode %d", cfg->mode);
@@ -193,7 +212,11 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad stage_obj_struct");
   if (cfg->critic_struct < 0 || cfg->critic_struct > 3)
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad critic_struct");
-  const int ds = kDims[cfg->sys_id][0], du = kDims[cfg->sys_id][1], np = kDims[cfg->sys_id][2];
+  const int ds = rtc ? rd.ds : kDims[cfg->sys_id][0], du = rtc ? rd.du : kDims[cfg->sys_id][1], np = rtc ? rd.np : kDims[cfg->sys_id][2];
+  if (rtc && cfg->mode != RCG_MODE_MPC)
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time runs MPC only (no RQL / SQL critic kernels)");
+  if (rtc && (cfg->flags & RCG_FLAG_DISTURB))
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time has no disturbance model");
   // (the reference's horizon is unbounded, controllers.py:965.  Rows of up to RCG_MAX_ROW reals are staged in LDS tiles; longer
   // ones are walked straight from HBM by the generic decision kernel, and the optimiser / search keep their per-wave LDS
   // budget: they refuse - before touching anything - a horizon their working set does not fit, rcg.h)
@@ -255,7 +278,9 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->order_ev = nullptr;
   h->release_ev = nullptr;
   memset(h->last, 0, sizeof h->last);
-  h->sys = cfg->sys_id == RCG_SYS_3WROBOT ? &kVt3WRobot : (cfg->sys_id == RCG_SYS_3WROBOT_NI ? &kVt3WRobotNI : &kVt2Tank);
+  h->rtc = rtc;
+  h->sys = rtc ? &kVtRtc
+               : (cfg->sys_id == RCG_SYS_3WROBOT ? &kVt3WRobot : (cfg->sys_id == RCG_SYS_3WROBOT_NI ? &kVt3WRobotNI : &kVt2Tank));
   memset(h->prof_ms, 0, sizeof h->prof_ms);
   memset(h->prof_n, 0, sizeof h->prof_n);
   memset(h->f, 0, sizeof h->f);
@@ -796,7 +821,8 @@ static bool ticks_rows_stay_close(const rcg_handle* h, const void* cand, int32_t
 int rcg_control_tick_n(rcg_handle* h, const void* cand, int32_t K, int32_t T) {
   if (!h) return RCG_ERR_BAD_ARG;
   if (T < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_control_tick_n: T must be >= 1");
-  if (T > 1 && h->cfg.mode == RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch &&
+  // (a system registered at run time has no k_ticks: the loop of single ticks below)
+  if (T > 1 && h->cfg.mode == RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch && !h->rtc &&
       ticks_rows_stay_close(h, cand, K)) {
     // MPC (any stage-cost structure, with or without the disturbance model): k_ticks keeps the env in registers and, for a
     // caller's tensor, the wave's candidate rows in LDS - every field ends as T single ticks leave it, bit for bit
@@ -923,6 +949,7 @@ int rcg_loop_step_begin(rcg_handle* h, const double* action_in, double step_h, i
   const bool critic = h->cfg.mode != RCG_MODE_MPC;
   const bool decide = flags & RCG_LOOP_DECIDE, push = critic && (flags & RCG_LOOP_PUSH), fit = push && (flags & RCG_LOOP_FIT);
   if (h->cfg.flags & RCG_FLAG_DISTURB) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: no disturbance model on this path");
+  if (h->rtc) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: not available for a system registered at run time");
   if (fit && h->cfg.n_critic - 1 < 1) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: an empty TD stack (Ncritic = 1) takes the separate calls");
   const int B = h->cfg.batch, ds = h->ds, du = h->du, dc = critic ? h->dc : 0, row = ds + du + 2 + dc;
   const size_t out_bytes = (size_t)B * row * sizeof(double), in_bytes = (size_t)B * du * sizeof(double);
@@ -1134,6 +1161,8 @@ int rcg_control_tick_nominal(rcg_handle* h, double ctrl_gain, const double* ctrl
   if (!h) return RCG_ERR_BAD_ARG;
   if (h->cfg.sys_id == RCG_SYS_2TANK)  // refuse before the env is stepped
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_nominal: the reference defines no nominal controller for 2tank");
+  if (h->rtc)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_nominal: not available for a system registered at run time");
   int rc = h->sys->sim_step(h, h->cfg.substeps_per_tick);
   if (rc) return rc;
   rc = h->sys->nominal(h, h->f[RCG_FIELD_STATE], h->f[RCG_FIELD_ACTION], nullptr, nullptr, h->cfg.batch, ctrl_gain,

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -47,6 +48,8 @@ struct rcg_handle {
   rcg::KParams<float> p32;
   rcg::KParams<double> p64;
   const struct SysVTable* sys;
+  const struct RtcSystem* rtc;  // a system registered at run time (rcg_rtc.hip); nullptr: a built-in one
+  std::map<std::string, hipFunction_t> rtc_fn;  // rcg_rtc.hip: name expression -> function resolved on this handle's device
   std::string err;
   // measurement (rcg_profile): event pairs recorded on `stream`, drained into totals on demand
   unsigned prof_mask;  // bit k: bracket launches of rcg_kernel k
@@ -257,3 +260,14 @@ struct SysVTable {
               double* out, double* flag, double seq);
 };
 extern const SysVTable kVt3WRobot, kVt3WRobotNI, kVt2Tank;
+
+// Systems registered at run time (rcg_register_system, rcg_rtc.hip): the registry entry of `sys_id` and its dimensions, or
+// nullptr for an id nobody registered.  Every such handle shares kVtRtc; the launchers find their system through h->rtc.
+struct RtcDims {
+  int ds, du, np;
+  bool has_jac;  // the policy defines jac_T: k_actor_opt is available
+};
+const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
+extern const SysVTable kVtRtc;
+// sets the thread's error text (rcg_last_error(NULL)) without rcg_fail's length limit: hipRTC's log
+void rcg_set_thread_error(const std::string& text);

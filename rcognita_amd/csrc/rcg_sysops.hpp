@@ -140,18 +140,25 @@ static int op_critic_cost(rcg_handle* h, const void* w, void* Jc) {
   });
 }
 
+// the env step's arguments: the handle's own fields (k_sim, k_sim_v, k_sim_dist; rcg_rtc.hip)
+template <typename real>
+static SimArgs<real> sim_args(const rcg_handle* h, int32_t n_substeps) {
+  SimArgs<real> A;
+  A.state = (real*)h->f[RCG_FIELD_STATE];
+  A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  A.action = (const real*)h->f[RCG_FIELD_ACTION];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  A.n_sub = n_substeps;
+  return A;
+}
+
 template <typename Sys>
 int op_sim_step(rcg_handle* h, int32_t n_substeps) {
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
-    SimArgs<real> A;
-    A.state = (real*)h->f[RCG_FIELD_STATE];
-    A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-    A.action = (const real*)h->f[RCG_FIELD_ACTION];
-    A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    A.accum = (real*)h->f[RCG_FIELD_ACCUM];
-    A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-    A.n_sub = n_substeps;
+    const SimArgs<real> A = sim_args<real>(h, n_substeps);
     ProfScope prof_scope(h, RCG_KERNEL_SIM);
     if (h->cfg.flags & RCG_FLAG_DISTURB) {  // full state [state, disturb] (rcg_disturb.hpp)
       SimDistArgs<real> D;
@@ -370,15 +377,38 @@ template <typename Sys>
 int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand);
 
 // ---- k_actor / k_actor_dma ---------------------------------------------------------------------
-// `sim_first`: rcg_control_tick (MPC) - run the env step of the tick before the decision.
-template <typename Sys, typename real>
-static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K, const void* obs,
-                        const void* state_sys, const void* w, void* J, void* action, void* best_J, int32_t* best_idx,
-                        bool tick, bool sim_first) {
-  constexpr int DU = Sys::DU;
+// The decision step's launch geometry: what launch_actor decides from runtime values alone - row length, K, the system's
+// dimensions and observation-target preset, element size, batch, mode and stage cost - before it picks a kernel instance.
+// The built-in systems' launcher below and the runtime-compiled systems' one (rcg_rtc.hip) both take it from actor_plan, so a
+// system registered at run time gets the grid, envs per wave, residency and LDS request of a built-in one of the same shape.
+struct ActorPlan {
+  int R;                       // reals per candidate row (Nactor * du)
+  size_t row_bytes;
+  bool long_row;               // rows beyond RCG_MAX_ROW: k_actor's DIRECT instance, no LDS tile
+  bool generic, tgt;           // k_actor's GENERIC (not MPC with a diagonal stage cost) and TGT instance parameters
+  int wpb;                     // k_actor: waves per block, dynamic LDS, blocks
+  size_t lds;
+  unsigned blocks;
+  int variant;                 // k_actor_dma / k_actor_dma_packed variant (DMA_*)
+  bool dma_ok, pack_ok;        // the shape goes to k_actor_dma / k_actor_dma_packed
+  bool fuse_sim;               // k_actor_dma_packed steps its own envs in its prologue (sim_first)
+  long pack_gpw;               // k_actor_dma_packed: envs per wave, grid, LDS request
+  dim3 pack_grid;
+  size_t pack_lds;
+  long dma_gpw;                // k_actor_dma: envs per wave, grid, LDS request, J staged per wave
+  dim3 dma_grid;
+  size_t dma_lds;
+  int dma_jwave;
+};
+
+// `sim_first`: rcg_control_tick (MPC) - run the env step of the tick before the decision.  Fills the kernel arguments common to
+// every instance and the plan; returns RCG_OK or the refusal of a bad argument (nothing launched).
+template <typename real>
+static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_tgt, const void* cand, int K, const void* obs,
+                      const void* state_sys, const void* w, void* J, void* action, void* best_J, int32_t* best_idx, bool tick,
+                      bool sim_first, ActorArgs<real>& A, ActorPlan& L) {
   const rcg_cfg& c = h->cfg;
   if (K < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: K must be >= 1", who);
-  ActorArgs<real> A;
   memset(&A, 0, sizeof A);
   A.cand = (const real*)cand;
   A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
@@ -424,6 +454,8 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
   }
   const int R = c.n_actor * DU;
   const size_t row_bytes = (size_t)R * sizeof(real);
+  L.R = R;
+  L.row_bytes = row_bytes;
   A.vec_ok = (cand && row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
   const long B = c.batch;
   const long n_waves = (B + A.G - 1) / A.G;
@@ -435,10 +467,15 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
   while (wpb > 1 && lds_per_wave * wpb > 64 * 1024) wpb >>= 1;
   size_t lds = lds_per_wave * wpb;
   if (cand && (size_t)dev_knobs().plain_lds > lds) lds = (size_t)dev_knobs().plain_lds;  // residency experiments
-  const unsigned blocks = (unsigned)((n_waves + wpb - 1) / wpb);
+  L.long_row = long_row;
+  L.wpb = wpb;
+  L.lds = lds;
+  L.blocks = (unsigned)((n_waves + wpb - 1) / wpb);
   const KParams<real>& P = params<real>(h);
   const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
   const bool tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  L.generic = generic;
+  L.tgt = tgt;
 
   // Production shape -> k_actor_dma (rcg_actor_dma.hpp): streamed candidates, K >= 33 with K * R * esz % 16 == 0 (33 .. 63: one
   // ragged tile per env - K = 48: 4.6 TB/s against 2.9 on k_actor, K = 36: 3.6 against 2.3 (RQL: 3.1 x, profiles/r04_ab_min_k.txt); at K <= 32 k_actor, which packs 64 / K envs into a tile,
@@ -455,12 +492,12 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
   // HBM peak at the C2 shape: profiles/r06_generic_stream_probe_*.txt)
   // (a diagonal quadratic cost with a target on a robot stays on k_actor's target instance: 0.78 of the peak there against 0.75 on
   // DMA_MPC_GEND, and its gamma == 1 accumulation - per component - is the one k_ticks re-walks the rows with)
-  const bool std_cost = P.stage_kind == 0 && (tgt == Sys::TGT || !tgt);
+  const bool std_cost = P.stage_kind == 0 && (tgt == sys_tgt || !tgt);
   const bool gen_cost = c.mode == RCG_MODE_MPC && P.stage_kind != 0 && !knobs.force_plain;
   // RQL with such a stage cost (or a target its system's preset has not): DMA_RQL_GEN_* (stage_any per step); SQL has no stage
   // cost inside the rollout - its instances serve any stage structure (only upd_accum_obj sees it)
   const bool gen_rql = c.mode == RCG_MODE_RQL && !std_cost && !knobs.force_plain;
-  const bool sql_any = c.mode == RCG_MODE_SQL && (tgt == Sys::TGT || !tgt);
+  const bool sql_any = c.mode == RCG_MODE_SQL && (tgt == sys_tgt || !tgt);
   int variant;
   if (gen_cost)
     variant = (P.stage_kind & STAGE_FULL) ? DMA_MPC_GENF : DMA_MPC_GEND;
@@ -470,23 +507,138 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
     variant = (gen_rql ? DMA_RQL_GEN_0 : DMA_RQL_0) + c.critic_struct;
   else
     variant = DMA_SQL_0 + c.critic_struct;
-  const size_t wslot = (size_t)4 * dma_wslot((int)esz, variant, Sys::DS, DU);  // critic weights parked in LDS (> 9 of them)
+  L.variant = variant;
+  const size_t wslot = (size_t)4 * dma_wslot((int)esz, variant, DS, DU);  // critic weights parked in LDS (> 9 of them)
   // (an env's rows must be a whole number of 16-byte pieces, K * R * esz % 16 == 0 - any K for rows of 16 n bytes such as C2's
   // 80, every 4th K for the shortest rows: then every env starts 16-B aligned and a ragged last tile ends on a piece)
   const bool slab16 = ((size_t)K * row_bytes) % 16 == 0;
   // (RQL / SQL without a packed instance - f64 with more than 18 weights: one ragged tile already from K = 20, where it
   // overtakes k_actor: 66 against 105 us at K = 24, 65 against 50 at K = 16; profiles/r04_ab_min_k.txt)
   const int dma_min_k = (c.mode != RCG_MODE_MPC && knobs.dma_min_k > 20) ? 20 : knobs.dma_min_k;
-  const bool dma_ok = cand && ((uintptr_t)cand % 16) == 0 && K >= dma_min_k && slab16 && R <= dma_max_row<real>() &&
-                      (std_cost || gen_cost || gen_rql || sql_any) && mode_ok && !knobs.force_plain &&
-                      // J staging must fit next to the tiles (one block per CU then)
-                      !(A.J && 4 * tile + wslot + 4 * esz * K > (size_t)160 * 1024);
+  L.dma_ok = cand && ((uintptr_t)cand % 16) == 0 && K >= dma_min_k && slab16 && R <= dma_max_row<real>() &&
+             (std_cost || gen_cost || gen_rql || sql_any) && mode_ok && !knobs.force_plain &&
+             // J staging must fit next to the tiles (one block per CU then)
+             !(A.J && 4 * tile + wslot + 4 * esz * K > (size_t)160 * 1024);
   // Few candidates per env (4 <= K <= 32, whole 16-byte pieces per env) -> k_actor_dma_packed (rcg_actor_dma_packed.hpp): 64 / K envs
-  // share a DMA tile (MPC; RQL / SQL with at most 36 dwords of critic weights - otherwise the launcher below finds no
+  // share a DMA tile (MPC; RQL / SQL with at most 36 dwords of critic weights - otherwise the launcher finds no
   // instance and the tick goes on to k_actor_dma / k_actor).  J staging (operator mode) must fit next to the four tiles.
   const int pack_g = (K >= 4 && K <= 32) ? 64 / K : 0;  // envs per tile
-  const bool pack_ok = cand && ((uintptr_t)cand % 16) == 0 && pack_g >= 2 && slab16 && R <= dma_max_row<real>() &&
-                       P.stage_kind == 0 && mode_ok && (tgt == Sys::TGT || !tgt) && !knobs.force_plain && !knobs.no_pack;
+  L.pack_ok = cand && ((uintptr_t)cand % 16) == 0 && pack_g >= 2 && slab16 && R <= dma_max_row<real>() && P.stage_kind == 0 &&
+              mode_ok && (tgt == sys_tgt || !tgt) && !knobs.force_plain && !knobs.no_pack;
+  // The env step of the tick (Simulator.sim_step) precedes the decision: its own launch (k_sim, 6.8 us at C2) - except in front
+  // of k_actor_dma_packed, whose launches are short enough (11-31 us) for the k_sim launch and the gap behind it to be 15-20 %
+  // of the tick: there the wave steps its own envs in its prologue (rcg_actor_dma_packed.hpp)
+  L.fuse_sim = L.pack_ok && tick && sim_first && !obs && !state_sys && !A.J &&
+               !(c.flags & (RCG_FLAG_DISTURB | RCG_FLAG_ACCUM_EVERY_SUBSTEP)) && !knobs.no_tick_fuse;
+  {
+    // a wave owns gpw = G * 2^n <= 64 consecutive envs (their results wait in its lanes); these launches are small (K = 16,
+    // B = 65536, Nactor = 10: 84 MB), so the grid is kept at >= 4096 waves and 4 blocks per CU stay resident
+    long gpw = pack_g;
+    while (pack_g > 0 && gpw * 2 <= 64 && B / (gpw * 2) >= 4096) gpw *= 2;
+    if (pack_g > 0 && knobs.gpw > 0 && knobs.gpw % pack_g == 0 && knobs.gpw <= 64) gpw = knobs.gpw;  // (dev build only)
+    const long pw = gpw > 0 ? (B + gpw - 1) / gpw : 0;
+    const size_t full_tile = (size_t)64 * R * esz;
+    size_t lds_req = 4 * full_tile + (A.J ? 4 * esz * (size_t)gpw * K : 0) + (L.fuse_sim ? 4 * esz * 2 * DS * 64 : 0);
+    const size_t cap = knobs.per_cu == 2 ? (size_t)56 * 1024 : (knobs.per_cu == 8 ? 0 : (size_t)36 * 1024);
+    if (lds_req < cap) lds_req = cap;  // 4 resident blocks per CU (dev build: RCG_PER_CU = 2 | 8)
+    L.pack_gpw = gpw;
+    L.pack_grid = dim3((unsigned)((pw + 3) / 4));
+    L.pack_lds = lds_req;
+  }
+  {
+    // Launch geometry, measured on MI355X at C2 (B = 65536, K = 256, N = 10; DESIGN.md 4):
+    //  * residency: 2 blocks (8 waves) per CU stream faster than 8 blocks per CU - 0.204 ms against 0.213-0.218 ms.
+    //    The dynamic-LDS request is raised to 56 KB so that at most two blocks fit into the CU's 160 KB;
+    //  * envs per wave (gpw): each wave writes the results of its gpw envs once, coalesced, so gpw >= 4 turns 6
+    //    scattered 4-byte writes per env into 16-64-byte segments; powers of two only (3, 6 measured 2-3 % slower);
+    //  * rounds: the grid must be several times the 512 resident blocks so that the CUs stay balanced (single-round
+    //    grids that do not divide evenly over 256 CUs lost 10 %: gpw = 20, 28, 48) - gpw is the largest power of
+    //    two <= 16 that still leaves >= 8192 waves.
+    const long Bn = h->sub_hi > 0 ? h->sub_hi - h->sub_lo : B;  // envs of this launch (a half of a split tick)
+    long gpw = 1;
+    while (gpw < 16 && Bn / (gpw * 2) >= 8192) gpw *= 2;
+    if (knobs.gpw > 0) gpw = knobs.gpw;
+    gpw = gpw < 1 ? 1 : (gpw > 64 ? 64 : gpw);
+    const long pw = (Bn + gpw - 1) / gpw;
+    // blocks per CU: 2 for rows of >= 20 reals (a block keeps R KiB in flight in f32), 4 for shorter rows, which need more
+    // waves to keep enough bytes on the wire (measured R = 6 ... 32 floats: 2 vs 4 differ by 1-3 % either side of
+    // R = 20, R = 10 with 2 blocks/CU is 9 % slower than with 4; 8 blocks/CU is 5-15 % slower than the better of the two)
+    // ... and 4 as well when a wave's whole slab is short (< 16 Ki reals: K = 64 at Nactor = 10 is 8 tiles per wave - the launch
+    // is ramp-up and tail, more resident waves fill it better: 5.15 -> 5.57 TB/s)
+    // (both thresholds count ELEMENTS - 16 Ki per wave, rows of 20 - since round 6: measured in f32 at first and kept in bytes, they
+    // sent the float64 shapes K = 64 and Nactor = 5 to 2 blocks per CU, where 4 stream 5 % / 3 % faster: profiles/r06_sweep_f64_geometry.txt)
+    const bool long_slab = (size_t)gpw * K * row_bytes >= (size_t)16 * 1024 * esz;
+    // ... and 4 for the critic instances with many weights (>= 68 bytes of them: the robots' quad-lin / quadratic / quad-mix
+    // structures in f32, 2tank quad-lin in f64), which are bound by VALU issue, not by the stream: more resident waves hide
+    // more of it - 4-5 % on random weights, 8-11 % inside a closed loop (profiles/r04_per_cu_matrix.txt, r04_ab_per_cu.txt:
+    // SQL quad-lin 307 -> 280 us, SQL quadratic 261 -> 232); MPC and the small structures lose 1-2 % with 4
+    const bool valu_heavy = variant == DMA_MPC_GENF ||  // (35-77 fused multiply-adds per step of stage cost)
+                            variant >= DMA_RQL_GEN_0 ||
+                            ((dma_is_rql(variant) || dma_is_sql(variant)) && (size_t)dma_dc(dma_cs(variant), DS, DU) * esz >= 68);
+    const int per_cu = knobs.per_cu > 0 ? knobs.per_cu : ((row_bytes >= 20 * esz && long_slab && !valu_heavy) ? 2 : 4);
+    // J staging (operator mode): all envs of the wave when that fits under 64 KB next to the tiles, else env by env
+    const int jwave = (A.J && 4 * tile + wslot + 4 * esz * gpw * K <= (size_t)64 * 1024) ? 1 : 0;
+    size_t lds_req = 4 * tile + wslot + (A.J ? 4 * esz * K * (jwave ? gpw : 1) : 0);
+    if (knobs.lds_pad > 0) {
+      lds_req += (size_t)knobs.lds_pad;
+    } else if (knobs.lds_pad == 0) {  // RCG_LDS_PAD=-1: no residency cap
+      const size_t want = per_cu <= 2 ? (size_t)56 * 1024 : (per_cu <= 4 ? (size_t)36 * 1024 : 0);
+      if (lds_req < want) lds_req = want;
+    }
+    // (blocks of 4 waves = one wave per SIMD: blocks of 2 or 1 waves at the same 8 resident waves per CU measured
+    // 10-13 % slower)
+    L.dma_gpw = gpw;
+    L.dma_grid = dim3((unsigned)((pw + 3) / 4));
+    L.dma_lds = lds_req;
+    L.dma_jwave = jwave;
+  }
+  return RCG_OK;
+}
+
+// the arguments of the k_actor_dma_packed / k_actor_dma launch of a plan
+template <typename real>
+static ActorArgs<real> packed_args(const rcg_handle* h, const ActorArgs<real>& A, const ActorPlan& L) {
+  ActorArgs<real> Ap = A;
+  Ap.G = 64 / A.K;
+  Ap.gpw = (int)L.pack_gpw;
+  Ap.jwave = 1;
+  if (L.fuse_sim) {
+    Ap.sim_state = (real*)h->f[RCG_FIELD_STATE];
+    Ap.sim_state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+    Ap.sim_action = (const real*)h->f[RCG_FIELD_ACTION];
+    Ap.sim_status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+    Ap.sim_n_sub = h->cfg.substeps_per_tick;
+  }
+  return Ap;
+}
+template <typename real>
+static ActorArgs<real> dma_args(const rcg_handle* h, const ActorArgs<real>& A, const ActorPlan& L) {
+  ActorArgs<real> Ad = A;
+  Ad.gpw = (int)L.dma_gpw;
+  Ad.env_lo = h->sub_lo;
+  Ad.env_hi = h->sub_hi;
+  Ad.jwave = L.dma_jwave;
+  return Ad;
+}
+
+template <typename Sys, typename real>
+static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K, const void* obs,
+                        const void* state_sys, const void* w, void* J, void* action, void* best_J, int32_t* best_idx,
+                        bool tick, bool sim_first) {
+  const rcg_cfg& c = h->cfg;
+  ActorArgs<real> A;
+  ActorPlan L;
+  {
+    const int rc = actor_plan<real>(h, who, Sys::DS, Sys::DU, Sys::TGT, cand, K, obs, state_sys, w, J, action, best_J, best_idx,
+                                    tick, sim_first, A, L);
+    if (rc) return rc;
+  }
+  const KParams<real>& P = params<real>(h);
+  const DevKnobs& knobs = dev_knobs();
+  const int R = L.R, wpb = L.wpb, variant = L.variant;
+  const size_t lds = L.lds;
+  const unsigned blocks = L.blocks;
+  const bool generic = L.generic, tgt = L.tgt, dma_ok = L.dma_ok, pack_ok = L.pack_ok, fuse_sim = L.fuse_sim;
   // rcg_control_tick with the generated grid in the regime of the hand-packed rollout: env step and decision in ONE launch
   // (k_ticks_pk with T = 1 - what rcg_control_ticks runs, so the two entry points cannot differ by a bit)
   if (h->probe == 1) {  // rcg_control_tick asking, before it launches anything, whether this tick's decision runs on k_actor_dma
@@ -503,47 +655,23 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
         action == h->f[RCG_FIELD_ACTION] && best_J == h->f[RCG_FIELD_BEST_J] && (void*)best_idx == h->f[RCG_FIELD_BEST_IDX])
       return op_ticks<Sys>(h, 1, K, nullptr);
   }
-  // The env step of the tick (Simulator.sim_step) precedes the decision: its own launch (k_sim, 6.8 us at C2) - except in front
-  // of k_actor_dma_packed, whose launches are short enough (11-31 us) for the k_sim launch and the gap behind it to be 15-20 %
-  // of the tick: there the wave steps its own envs in its prologue (rcg_actor_dma_packed.hpp)
-  const bool fuse_sim = pack_ok && tick && sim_first && !obs && !state_sys && !A.J &&
-                        !(c.flags & (RCG_FLAG_DISTURB | RCG_FLAG_ACCUM_EVERY_SUBSTEP)) && !knobs.no_tick_fuse;
   if (sim_first && !fuse_sim) {
     int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
     if (rc) return rc;
   }
   ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
   if (pack_ok) {
-    // a wave owns gpw = G * 2^n <= 64 consecutive envs (their results wait in its lanes); these launches are small (K = 16,
-    // B = 65536, Nactor = 10: 84 MB), so the grid is kept at >= 4096 waves and 4 blocks per CU stay resident
-    long gpw = pack_g;
-    while (gpw * 2 <= 64 && B / (gpw * 2) >= 4096) gpw *= 2;
-    if (knobs.gpw > 0 && knobs.gpw % pack_g == 0 && knobs.gpw <= 64) gpw = knobs.gpw;  // (dev build only)
-    const long pw = (B + gpw - 1) / gpw;
-    const dim3 grid((unsigned)((pw + 3) / 4)), block(256);
-    const size_t full_tile = (size_t)64 * R * esz;
-    size_t lds_req = 4 * full_tile + (A.J ? 4 * esz * (size_t)gpw * K : 0) + (fuse_sim ? 4 * esz * 2 * Sys::DS * 64 : 0);
-    const size_t cap = knobs.per_cu == 2 ? (size_t)56 * 1024 : (knobs.per_cu == 8 ? 0 : (size_t)36 * 1024);
-    if (lds_req < cap) lds_req = cap;  // 4 resident blocks per CU (dev build: RCG_PER_CU = 2 | 8)
     const ProfPair pp = prof_take(h);  // a due ProfScope's pair travels in the dispatch
-    ActorArgs<real> Ap = A;
-    Ap.G = pack_g;
-    Ap.gpw = (int)gpw;
-    Ap.jwave = 1;
-    if (fuse_sim) {
-      Ap.sim_state = (real*)h->f[RCG_FIELD_STATE];
-      Ap.sim_state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-      Ap.sim_action = (const real*)h->f[RCG_FIELD_ACTION];
-      Ap.sim_status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-      Ap.sim_n_sub = c.substeps_per_tick;
-    }
+    const ActorArgs<real> Ap = packed_args(h, A, L);
+    const dim3 grid = L.pack_grid, block(256);
+    const size_t lds_req = L.pack_lds;
     // (no instance - RQL / SQL with more than 36 dwords of weights: the tick is served by k_actor_dma / k_actor below)
     const bool launched =
         variant < DMA_RQL_0    ? launch_dma_packed<Sys, real, 3>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b)
         : variant >= DMA_SQL_0 ? launch_dma_packed<Sys, real, 4>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b)
                                : launch_dma_packed<Sys, real, 5>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b);
     if (launched) {
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA_PACKED, variant | (fuse_sim ? 16 : 0), (int)gpw);
+      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA_PACKED, variant | (fuse_sim ? 16 : 0), (int)L.pack_gpw);
       HIPCHK(h, hipGetLastError());
       return RCG_OK;
     }
@@ -554,52 +682,9 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
     }
   }
   if (dma_ok) {
-    // Launch geometry, measured on MI355X at C2 (B = 65536, K = 256, N = 10; DESIGN.md 4):
-    //  * residency: 2 blocks (8 waves) per CU stream faster than 8 blocks per CU - 0.204 ms against 0.213-0.218 ms.
-    //    The dynamic-LDS request is raised to 56 KB so that at most two blocks fit into the CU's 160 KB;
-    //  * envs per wave (gpw): each wave writes the results of its gpw envs once, coalesced, so gpw >= 4 turns 6
-    //    scattered 4-byte writes per env into 16-64-byte segments; powers of two only (3, 6 measured 2-3 % slower);
-    //  * rounds: the grid must be several times the 512 resident blocks so that the CUs stay balanced (single-round
-    //    grids that do not divide evenly over 256 CUs lost 10 %: gpw = 20, 28, 48) - gpw is the largest power of
-    //    two <= 16 that still leaves >= 8192 waves.
-    const long Bn = h->sub_hi > 0 ? h->sub_hi - h->sub_lo : B;  // envs of this launch (a half of a split tick)
-    long gpw = 1;
-    while (gpw < 16 && Bn / (gpw * 2) >= 8192) gpw *= 2;
-    if (knobs.gpw > 0) gpw = knobs.gpw;
-    gpw = gpw < 1 ? 1 : (gpw > 64 ? 64 : gpw);
-    ActorArgs<real> Ad = A;
-    Ad.gpw = (int)gpw;
-    Ad.env_lo = h->sub_lo;
-    Ad.env_hi = h->sub_hi;
-    const long pw = (Bn + gpw - 1) / gpw;
-    const dim3 grid((unsigned)((pw + 3) / 4)), block(256);
-    // blocks per CU: 2 for rows of >= 20 reals (a block keeps R KiB in flight in f32), 4 for shorter rows, which need more
-    // waves to keep enough bytes on the wire (measured R = 6 ... 32 floats: 2 vs 4 differ by 1-3 % either side of
-    // R = 20, R = 10 with 2 blocks/CU is 9 % slower than with 4; 8 blocks/CU is 5-15 % slower than the better of the two)
-    // ... and 4 as well when a wave's whole slab is short (< 16 Ki reals: K = 64 at Nactor = 10 is 8 tiles per wave - the launch
-    // is ramp-up and tail, more resident waves fill it better: 5.15 -> 5.57 TB/s)
-    // (both thresholds count ELEMENTS - 16 Ki per wave, rows of 20 - since round 6: measured in f32 at first and kept in bytes, they
-    // sent the float64 shapes K = 64 and Nactor = 5 to 2 blocks per CU, where 4 stream 5 % / 3 % faster: profiles/r06_sweep_f64_geometry.txt)
-    const bool long_slab = (size_t)gpw * K * row_bytes >= (size_t)16 * 1024 * esz;
-    // ... and 4 for the critic instances with many weights (>= 68 bytes of them: the robots' quad-lin / quadratic / quad-mix
-    // structures in f32, 2tank quad-lin in f64), which are bound by VALU issue, not by the stream: more resident waves hide
-    // more of it - 4-5 % on random weights, 8-11 % inside a closed loop (profiles/r04_per_cu_matrix.txt, r04_ab_per_cu.txt:
-    // SQL quad-lin 307 -> 280 us, SQL quadratic 261 -> 232); MPC and the small structures lose 1-2 % with 4
-    const bool valu_heavy = variant == DMA_MPC_GENF ||  // (35-77 fused multiply-adds per step of stage cost)
-                            variant >= DMA_RQL_GEN_0 ||
-                            ((dma_is_rql(variant) || dma_is_sql(variant)) && (size_t)dma_dc(dma_cs(variant), Sys::DS, DU) * esz >= 68);
-    const int per_cu = knobs.per_cu > 0 ? knobs.per_cu : ((row_bytes >= 20 * esz && long_slab && !valu_heavy) ? 2 : 4);
-    // J staging (operator mode): all envs of the wave when that fits under 64 KB next to the tiles, else env by env
-    Ad.jwave = (A.J && 4 * tile + wslot + 4 * esz * gpw * K <= (size_t)64 * 1024) ? 1 : 0;
-    size_t lds_req = 4 * tile + wslot + (A.J ? 4 * esz * K * (Ad.jwave ? gpw : 1) : 0);
-    if (knobs.lds_pad > 0) {
-      lds_req += (size_t)knobs.lds_pad;
-    } else if (knobs.lds_pad == 0) {  // RCG_LDS_PAD=-1: no residency cap
-      const size_t want = per_cu <= 2 ? (size_t)56 * 1024 : (per_cu <= 4 ? (size_t)36 * 1024 : 0);
-      if (lds_req < want) lds_req = want;
-    }
-    // (blocks of 4 waves = one wave per SIMD: blocks of 2 or 1 waves at the same 8 resident waves per CU measured
-    // 10-13 % slower)
+    const ActorArgs<real> Ad = dma_args(h, A, L);
+    const dim3 grid = L.dma_grid, block(256);
+    const size_t lds_req = L.dma_lds;
     bool ok = false;
     const ProfPair pp = prof_take(h);  // a due ProfScope's pair travels in the dispatch
     if (variant >= DMA_RQL_GEN_0)
@@ -614,7 +699,7 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
       ok = launch_dma<Sys, real, 2>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
     if (!ok) prof_give_back(h, pp);
     if (ok) {  // (otherwise - unreachable for the rows dma_ok admits - k_actor below serves the tick: never refused half-way)
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, variant, (int)gpw);
+      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, variant, (int)L.dma_gpw);
       HIPCHK(h, hipGetLastError());
       return RCG_OK;
     }
@@ -633,7 +718,7 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
       return RCG_OK;
     }
   }
-  if (long_row) {
+  if (L.long_row) {
     if (tgt)
       RCG_LAUNCH(h, (k_actor<Sys, real, true, true, true, false, true>), dim3(blocks), dim3(64 * wpb), 0, A, P);
     else
@@ -678,6 +763,59 @@ int op_actor(rcg_handle* h, const char* who, const void* cand, int K, const void
   });
 }
 
+// k_actor_opt's arguments and launch shape for the handle (the built-in systems' launcher below and rcg_rtc.hip): fills A, the
+// waves per block and the block's LDS; refuses (nothing launched) a working set beyond the CU's 160 KB
+template <typename real>
+static int opt_plan(rcg_handle* h, int du, int32_t iters, const void* obs, const void* state_sys, const void* u_init, int shift,
+                    void* u_opt, void* action, void* best_J, int32_t* n_iter, bool tick, OptArgs<real>& A, int& wpb, size_t& lds) {
+  const rcg_cfg& c = h->cfg;
+  memset(&A, 0, sizeof A);
+  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
+  if (state_sys)
+    A.state_sys = (const real*)state_sys;
+  else if (obs)
+    A.state_sys = (const real*)obs;
+  else
+    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
+  if (c.mode != RCG_MODE_MPC && !A.w)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_optimize: RQL/SQL need critic weights (buffer_size > 0)");
+  A.u_init = (const real*)u_init;
+  A.u_opt = (real*)u_opt;
+  A.action_out = (real*)action;
+  A.best_J = (real*)best_J;
+  A.n_iter = n_iter;
+  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
+  A.step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
+  for (int i = 0; i < du; ++i) A.u0[i] = (real)c.action_init[i];
+  A.iters = iters;
+  A.shift = shift;
+  A.memory = opt_memory_of(h);
+  A.ftol = (real)h->opt_ftol;
+  A.dcw = c.mode != RCG_MODE_MPC ? h->dc : 0;
+  // waves per block: the waves of a block do not cooperate, so the block size only decides how many waves of LDS fit a CU's
+  // 160 KB: 4 (one per SIMD) unless 2 or 1 bring more waves onto the CU (quad-mix on the 3-wheel robot with 4 pairs: 20.4 KB
+  // per wave = ONE block of four, but seven blocks of one; long horizons in f64: N = 20, 4 pairs needs 70 KB per wave)
+  const size_t lds_wave = opt_wave_lds_bytes(h);
+  wpb = 4;
+  size_t on_cu = 0;
+  for (int cand_wpb = 4; cand_wpb >= 1; cand_wpb >>= 1) {
+    const size_t fit = lds_wave * cand_wpb ? ((size_t)160 * 1024 / (lds_wave * cand_wpb)) * cand_wpb : 0;
+    if (fit * 4 > on_cu * 5) {  // a smaller block must bring a quarter more waves: 9 single-wave blocks against 2 x 4 measured 10 % SLOWER
+                                // (MPC with 4 pairs, 18.1 KB per wave: one SIMD carries three waves and the second round is ragged)
+      on_cu = fit;
+      wpb = cand_wpb;
+    }
+  }
+  lds = lds_wave * wpb;
+  if (lds > (size_t)160 * 1024)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                    "rcg_actor_optimize: horizon %d with %d curvature pairs needs %zu B of LDS per wave (rcg_set_optimizer)",
+                    c.n_actor, opt_memory_of(h), lds_wave);
+  return RCG_OK;
+}
+
 template <typename Sys>
 int op_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* state_sys, const void* u_init,
                        int shift, void* u_opt, void* action, void* best_J, int32_t* n_iter, bool tick, bool sim_first) {
@@ -686,55 +824,17 @@ int op_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* state
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     OptArgs<real> A;
-    memset(&A, 0, sizeof A);
-    A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
-    if (state_sys)
-      A.state_sys = (const real*)state_sys;
-    else if (obs)
-      A.state_sys = (const real*)obs;
-    else
-      A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-    A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
-    if (c.mode != RCG_MODE_MPC && !A.w)
-      return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_optimize: RQL/SQL need critic weights (buffer_size > 0)");
-    A.u_init = (const real*)u_init;
-    A.u_opt = (real*)u_opt;
-    A.action_out = (real*)action;
-    A.best_J = (real*)best_J;
-    A.n_iter = n_iter;
-    A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-    A.step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
-    for (int i = 0; i < Sys::DU; ++i) A.u0[i] = (real)c.action_init[i];
-    A.iters = iters;
-    A.shift = shift;
-    A.memory = opt_memory_of(h);
-    A.ftol = (real)h->opt_ftol;
+    int wpb;
+    size_t lds;
+    {
+      const int rc = opt_plan<real>(h, Sys::DU, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, wpb, lds);
+      if (rc) return rc;
+    }
     const bool loop = h->loop_io.on;  // rcg_loop_step's one-launch sample: head and tail of the loop iteration in this launch
     if (loop)
       fill_loop_args<real>(h, A.loop, h->loop_io.act_in, h->loop_io.n_substeps, 1, 1, 1, h->loop_io.dc, h->loop_io.out,
                            h->loop_io.flag, h->loop_io.seq);
     const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
-    A.dcw = c.mode != RCG_MODE_MPC ? h->dc : 0;
-    // waves per block: the waves of a block do not cooperate, so the block size only decides how many waves of LDS fit a CU's
-    // 160 KB: 4 (one per SIMD) unless 2 or 1 bring more waves onto the CU (quad-mix on the 3-wheel robot with 4 pairs: 20.4 KB
-    // per wave = ONE block of four, but seven blocks of one; long horizons in f64: N = 20, 4 pairs needs 70 KB per wave)
-    const size_t lds_wave = opt_wave_lds_bytes(h);
-    int wpb = 4;
-    size_t on_cu = 0;
-    for (int cand_wpb = 4; cand_wpb >= 1; cand_wpb >>= 1) {
-      const size_t fit = lds_wave * cand_wpb ? ((size_t)160 * 1024 / (lds_wave * cand_wpb)) * cand_wpb : 0;
-      if (fit * 4 > on_cu * 5) {  // a smaller block must bring a quarter more waves: 9 single-wave blocks against 2 x 4 measured 10 % SLOWER
-                                  // (MPC with 4 pairs, 18.1 KB per wave: one SIMD carries three waves and the second round is ragged)
-        on_cu = fit;
-        wpb = cand_wpb;
-      }
-    }
-    const size_t lds = lds_wave * wpb;
-    if (lds > (size_t)160 * 1024)
-      return rcg_fail(h, RCG_ERR_UNSUPPORTED,
-                      "rcg_actor_optimize: horizon %d with %d curvature pairs needs %zu B of LDS per wave (rcg_set_optimizer)",
-                      c.n_actor, opt_memory_of(h), lds_wave);
     const dim3 grid(blocks_for(c.batch, wpb * OPT_G)), block(64 * wpb);  // a wave owns OPT_G envs
     const bool tgt = c.flags & RCG_FLAG_HAS_TARGET;
     if (tick && sim_first) {  // rcg_control_tick_opt (MPC): the env step of the tick, once every argument check has passed

@@ -111,6 +111,8 @@ class EngineConfig:
         if self.accum_every_substep:
             flags |= N.FLAG_ACCUM_EVERY_SUBSTEP
         if self.is_disturb:
+            if int(self.sys_id) not in N.DIM_DISTURB:
+                raise NotImplementedError("a system registered at run time has no disturbance model")
             dd = N.DIM_DISTURB[int(self.sys_id)]
             flags |= N.FLAG_DISTURB
             if self.pars_disturb is None or len(self.pars_disturb) != 3:
@@ -240,7 +242,7 @@ class Engine:
         self._pool, self._pool_bytes = {}, 0  # free list of small scratch allocations, by capacity (DeviceArray)
         L = N.lib()
         self.ds, self.du, self.npar = N.SYS_DIMS[cfg.sys_id]
-        self.dd = N.DIM_DISTURB[int(cfg.sys_id)]
+        self.dd = N.DIM_DISTURB.get(int(cfg.sys_id), 0)  # (a system registered at run time has no disturbance model)
         self.dy = self.ds
         self.B = int(cfg.batch)
         self.N = int(cfg.Nactor)

@@ -11,9 +11,14 @@ Same class names, constructor signature and method names as the reference, so a 
   right-hand side; here the noise comes from the counter-based generator of rcg_disturb.hpp (key ``seed``): a
   ``System`` object called directly draws one vector per call, a ``Simulator`` one per RK4 substep and env;
 * ``is_dyn_ctrl`` is rejected: no preset sets it and the reference's dynamic-controller branch is itself broken
-  (SURVEY.md 8a row 1).
+  (SURVEY.md 8a row 1);
+* your own system: instead of overriding ``_state_dyn`` in Python, a subclass sets ``hip_policy`` to the source of a policy
+  struct in the shape of the built-ins (rcognita_amd/csrc/rcg_systems.hpp).  The class is compiled for the GPU on its first
+  construction (``_native.register_system``) and runs the MPC path; INTEGRATION.md, "Your own system".
 """
 from __future__ import annotations
+
+import re
 
 import numpy as np
 
@@ -24,12 +29,20 @@ from .engine import Engine, EngineConfig
 class System:
     """Interface class of dynamical systems a.k.a. environments (rcognita/systems.py:17-253)."""
 
-    _sys_id = None  # set by the concrete systems
+    _sys_id = None  # set by the concrete systems (a ``hip_policy`` class: by its registration)
+    hip_policy = None  # source of a policy struct (``struct Name { ... };``): a system compiled at run time
+    _hip_info = None  # the registration of a ``hip_policy`` class (``_native.register_system``)
     _ctrl_ref = None  # weak reference to the CtrlOptPred built around this system (_register_controller)
     name = "system"
 
     def __init__(self, sys_type, dim_state, dim_input, dim_output, dim_disturb, pars=[], ctrl_bnds=[], is_dyn_ctrl=0,
                  is_disturb=0, pars_disturb=[], dtype="f64", device=0, seed=0):
+        if type(self).hip_policy is not None:
+            if is_disturb:
+                raise NotImplementedError("a system compiled from hip_policy has no disturbance model (is_disturb=1)")
+            if type(self).out is not System.out:
+                raise NotImplementedError("a system compiled from hip_policy has output = state: `out` cannot be overridden")
+            self._register_hip_policy(dim_state, dim_input, pars)
         if self._sys_id is None:
             raise NotImplementedError(
                 "only the built-in systems (Sys3WRobot, Sys3WRobotNI, Sys2Tank) run on the native path; "
@@ -58,6 +71,34 @@ class System:
         self._noise_calls = 0  # draws made by direct calls of _disturb_dyn / closed_loop_rhs on this object
 
     # ---- native plumbing ---------------------------------------------------------------------
+    @classmethod
+    def _register_hip_policy(cls, dim_state, dim_input, pars):
+        """Compile the class's ``hip_policy`` once (the registry returns the same id for the same source).  The struct is the
+        first ``struct <Name> {`` outside comments; its dimensions are its own ``DS`` / ``DU`` / ``NP`` where they are written
+        as integer literals (``static constexpr int DS = 2, DU = 1, NP = 3;``), else the constructor's - which the compiler
+        then checks against the struct (a mismatch is a ValueError, like the built-ins' dimension check)."""
+        if cls.__dict__.get("_hip_info") is not None:
+            return
+        src = cls.hip_policy
+        code = re.sub(r"//[^\n]*|/\*.*?\*/", " ", src, flags=re.S)  # the regexes below read code, not comments
+        m = re.search(r"\bstruct\s+([A-Za-z_]\w*)\s*\{", code)
+        if m is None:
+            raise ValueError("hip_policy must define `struct <Name> { ... };`")
+        body = code[m.end():]
+        dims = []
+        for key, given in (("DS", dim_state), ("DU", dim_input), ("NP", len(pars))):
+            d = re.search(r"\b%s\s*=\s*(\d+)\s*[,;]" % key, body)
+            dims.append(int(d.group(1)) if d else int(given))
+        try:
+            info = N.register_system(m.group(1), src, *dims)
+        except N.NativeError as e:
+            if e.code == N.ERR_BAD_ARG and "differs from the declared" in str(e):
+                raise ValueError(f"{cls.__name__}: the dimensions (state, input, pars) = {tuple(dims)} do not match the struct "
+                                 f"{m.group(1)}: {e}") from None
+            raise
+        cls._hip_info = info
+        cls._sys_id = info["sys_id"]
+
     def _disturb_cfg(self):
         if not self.is_disturb:
             return {}

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""A system compiled at run time (rcg_register_system) next to a built-in one of the same kernel shape.
+
+Registers the pendulum of INTEGRATION.md (DS 2, DU 1, NP 3; wall time of the call = probe + f32 + f64 core programs), creates
+one handle per element type and times the first streamed decision (it compiles k_actor_dma at the handle's row length), then
+times the streamed f64 tick at 65 536 envs x 256 candidates x Nactor 10 from the dispatches' own stamps (rcg_profile) on the
+pendulum, on the small-angle pendulum (no trigonometry) and on Sys2Tank (same DS / DU, same kernel shape), as a fraction of
+8 TB/s of candidate bytes.  GPU box only; no torch.
+
+    python tools/user_system_probe.py [B] [K] [Nactor]
+"""
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from rcognita_amd import Engine, EngineConfig  # noqa: E402
+from rcognita_amd import _native as N  # noqa: E402
+
+# the pendulum of INTEGRATION.md §5: state (angle, rate), action (torque), pars (m, g, l)
+PENDULUM = r"""
+struct PendulumT {
+  static constexpr int DS = 2, DU = 1, NP = 3;
+  template <typename real>
+  struct Pre {
+    real g_l, inv_ml2;
+  };
+  template <typename real>
+  __device__ __forceinline__ static Pre<real> prepare(const real* p) {
+    return {p[1] / p[2], (real)1 / (p[0] * p[2] * p[2])};
+  }
+  template <typename real, bool HW = false>
+  __device__ __forceinline__ static void rhs(const Pre<real>& q, const real* x, const real* u, real* d) {
+    real s, c;
+    sincos_sel<real, HW>(x[0], &s, &c);
+    d[0] = x[1];
+    d[1] = fma_r(q.inv_ml2, u[0], -q.g_l * s);
+  }
+  template <typename real, bool HW = false>
+  __device__ __forceinline__ static void jac_T(const Pre<real>& q, const real* x, const real*, const real* lam, real* ax,
+                                               real* bu) {
+    real s, c;
+    sincos_sel<real, HW>(x[0], &s, &c);
+    ax[0] = -q.g_l * c * lam[1];
+    ax[1] = lam[0];
+    bu[0] = q.inv_ml2 * lam[1];
+  }
+};
+"""
+# the same shape without trigonometry (the small-angle pendulum, sin x ~ x): separates the cost of the f64 sine in the rollout
+# from everything else the runtime path does
+PENDULUM_LIN = PENDULUM.replace("sincos_sel<real, HW>(x[0], &s, &c);", "s = x[0];\n    c = (real)1;")
+
+B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
+K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
+NH = int(sys.argv[3]) if len(sys.argv) > 3 else 10
+PEAK = 8e12
+
+info = N.register_system("PendulumProbe", PENDULUM.replace("PendulumT", "PendulumProbe"), 2, 1, 3)
+print(f"hiprtc {info['hiprtc']}: rcg_register_system {info['seconds']:.2f} s (probe + f32 + f64 core programs)")
+lin = N.register_system("PendulumLinProbe", PENDULUM_LIN.replace("PendulumT", "PendulumLinProbe"), 2, 1, 3)
+
+
+def engine(sid, dtype, pars):
+    return Engine(EngineConfig(sys_id=sid, batch=B, dtype=dtype, Nactor=NH, pars=pars, ctrl_bnds=np.array([[-5.0, 5.0]]),
+                               R1=np.diag([10.0, 1.0, 0.1]), dt_sim=0.01, sampling_time=0.01, pred_step_size=0.02))
+
+
+rng = np.random.default_rng(0)
+for dtype in ("f32", "f64"):
+    e = engine(info["sys_id"], dtype, [1.3, 9.81, 0.7])
+    e.set_state(rng.uniform(-1, 1, (B, 2)))
+    cand = e.to_device(rng.uniform(-5, 5, (B, K, NH, 1)))
+    t0 = time.perf_counter()
+    e.control_tick(cand)
+    e.synchronize()
+    print(f"{dtype}: first streamed tick (compiles {e.last_launch()['kernel']} at R = {NH}) {time.perf_counter() - t0:.2f} s")
+    e.close()
+
+rows = []
+for name, sid, pars in (("pendulum (runtime)", info["sys_id"], [1.3, 9.81, 0.7]),
+                        ("small-angle (runtime)", lin["sys_id"], [1.3, 9.81, 0.7]),
+                        ("Sys2Tank (built-in)", N.SYS_2TANK, [15.0, 15.0, 1.0, 1.0, 0.1])):
+    e = engine(sid, "f64", pars)
+    e.set_state(rng.uniform(0, 1, (B, 2)))
+    cand = e.to_device(rng.uniform(-5, 5, (B, K, NH, 1)))
+    for _ in range(5):
+        e.control_tick(cand)
+    e.synchronize()
+    e.profile([N.KERNEL_ACTOR])
+    for _ in range(50):
+        e.control_tick(cand)
+    e.synchronize()
+    t = np.median(e.profile_samples(N.KERNEL_ACTOR)) * 1e-3
+    frac = B * K * NH * 8 / t / PEAK
+    rows.append((name, e.last_launch(), t, frac))
+    e.close()
+for name, ll, t, frac in rows:
+    print(f"{name:22s} {ll['kernel']} variant {ll['variant']} gpw {ll['envs_per_wave']}: decision {t * 1e6:.1f} us, "
+          f"{frac:.3f} of 8 TB/s")
