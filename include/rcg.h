@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 120 /* 119 + rcg_register_system, rcg_rtc_version, rcg_system_info (systems compiled at run time) */
+#define RCG_VERSION 121 /* 120 + output maps y = out(x) of registered systems: rcg_system_output_info, rcg_out */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -179,7 +179,12 @@ int rcg_device_count(void);
 /* A system of your own, compiled at run time for gfx950 (hipRTC) against the library's kernel headers.  `policy_src` is a
  * complete `struct <name> { ... };` in the shape of the built-ins ("Systems registered at run time"): DS, DU, NP,
  * template <typename real> struct Pre, prepare, rhs<real, HW>; optional jac_T (enables rcg_actor_optimize /
- * rcg_control_tick_opt), TGT, ZW_PRESET, SHARED_U1 (defaults false, 0, 0).  It may use rcg_math.hpp (sincos_sel, fma_r, ...) and
+ * rcg_control_tick_opt), TGT, ZW_PRESET, SHARED_U1 (defaults false, 0, 0), and the output map (systems.py:185): DY
+ * (dim_output, default DS), out<real, HW>(q, x, y) (y = out(x); default y = x) and out_jac_T<real, HW>(q, x, gy, gx)
+ * (gx = (d out / d x)^T gy; with out, rcg_actor_optimize needs it).  1 <= DY <= RCG_MAX_DS (RCG_ERR_UNSUPPORTED otherwise); a
+ * DY other than DS without out is RCG_ERR_BAD_ARG.  With out every observation of the handle is [DY][B] (rcg_stage_obj,
+ * rcg_actor_cost, rcg_actor_argmin, rcg_actor_optimize), R1 / R2 are (DY + du)^2 and the target has DY entries; a tick
+ * observes out(STATE).  It may use rcg_math.hpp (sincos_sel, fma_r, ...) and
  * the device math library.  The declared ds / du / np must match the struct (RCG_ERR_BAD_ARG otherwise) and stay within
  * RCG_MAX_DS / RCG_MAX_DU / RCG_MAX_PARS (RCG_ERR_UNSUPPORTED otherwise).  Compiles the f32 and f64 programs before it returns
  * (seconds; no device needed); a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error(NULL).  The same name and
@@ -191,9 +196,13 @@ int rcg_device_count(void);
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
-/* dimensions of a built-in or registered system, and whether it has the optimiser (jac_T; every built-in one has);
- * any pointer may be NULL.  RCG_ERR_BAD_ARG for an id that names no system. */
+/* dimensions of a built-in or registered system, and whether it defines jac_T (every built-in one does); any pointer may be
+ * NULL.  RCG_ERR_BAD_ARG for an id that names no system.  rcg_actor_optimize needs jac_T, and with an output map out_jac_T
+ * too (rcg_system_output_info). */
 int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32_t* has_jac);
+/* output map of a built-in or registered system: dim_output, whether the policy defines out and out_jac_T (built-ins: ds, 0, 0);
+ * any pointer may be NULL.  RCG_ERR_BAD_ARG for an id that names no system. */
+int rcg_system_output_info(int32_t sys_id, int32_t* dy, int32_t* has_out, int32_t* has_out_jac);
 
 /* ---- life cycle: System.__init__ (systems.py:69-145), Simulator.__init__ (simulator.py:71-154),
  *      CtrlOptPred.__init__ (controllers.py:811-1044) ------------------------------------------ */
@@ -251,10 +260,14 @@ int rcg_rhs_full(rcg_handle* h, const void* state, const void* disturb, const vo
 int rcg_disturb_noise(rcg_handle* h, void* bits_out, void* xi_out);
 /* CtrlOptPred.stage_obj (controllers.py:1063-1084): obs [dy][n], act [du][n] -> out [n]. */
 int rcg_stage_obj(rcg_handle* h, const void* obs, const void* act, void* out, int32_t n);
+/* System.out (systems.py:185): state [ds][n] -> obs [dy][n], in the handle's element type; the handle's per-env parameters
+ * when n is its batch.  A system without an output map copies (dy = ds). */
+int rcg_out(rcg_handle* h, const void* state, void* obs, int32_t n);
 /* CtrlOptPred._critic (controllers.py:1192-1214): w [dc][n] -> out [n]. */
 int rcg_critic(rcg_handle* h, const void* obs, const void* act, const void* w, void* out, int32_t n);
 /* CtrlOptPred._actor_cost (controllers.py:1273-1328) for K candidate sequences per env.
- * cand [B][K][N][du]; obs [dy][B] and state_sys [ds][B] (NULL: the handle's STATE for both);
+ * cand [B][K][N][du]; obs [dy][B] and state_sys [ds][B] (NULL: the handle's STATE for both - observed as out(STATE); an obs
+ * without state_sys stands for both only when dy == ds, RCG_ERR_BAD_ARG otherwise);
  * w [dc][B] (NULL: the handle's W_CRITIC; ignored in MPC mode) -> J [B][K]. */
 int rcg_actor_cost(rcg_handle* h, const void* cand, int32_t K, const void* obs, const void* state_sys,
                    const void* w, void* J);

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librcg.so")
 
 # ---- enums (include/rcg.h) -------------------------------------------------------------------
-RCG_VERSION = 120
+RCG_VERSION = 121
 OK, ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_NONFINITE = 0, -1, -2, -3, -4, -5
 SYS_3WROBOT, SYS_3WROBOT_NI, SYS_2TANK = 0, 1, 2
 MODE_MPC, MODE_RQL, MODE_SQL = 0, 1, 2
@@ -39,6 +39,7 @@ CRITIC_IDS = {"quad-lin": CRITIC_QUAD_LIN, "quadratic": CRITIC_QUADRATIC, "quad-
               "quad-mix": CRITIC_QUAD_MIX}
 SYS_IDS = {"3wrobot": SYS_3WROBOT, "3wrobotNI": SYS_3WROBOT_NI, "2tank": SYS_2TANK}
 SYS_DIMS = {SYS_3WROBOT: (5, 2, 2), SYS_3WROBOT_NI: (3, 2, 0), SYS_2TANK: (2, 1, 5)}  # ds, du, n_pars (+ registered systems)
+SYS_DY = {}  # dim_output of the registered systems (register_system; sys_dy)
 SYS_USER_BASE = 16  # ids of systems registered at run time (register_system) start here
 MAX_DS, MAX_DU, MAX_PARS = 5, 2, 5
 
@@ -52,7 +53,7 @@ SYMBOLS = [
     "rcg_control_tick_nominal", "rcg_rhs_full", "rcg_disturb_noise", "rcg_episode_reset", "rcg_episode_stats", "rcg_tick_count", "rcg_set_tick_count", "rcg_profile", "rcg_profile_read",
     "rcg_profile_samples", "rcg_last_launch", "rcg_kernel_name", "rcg_wait_stream", "rcg_nominal_theta", "rcg_set_optimizer", "rcg_set_optimizer_tol", "rcg_set_tick_parts", "rcg_join", "rcg_loop_step", "rcg_loop_step_begin", "rcg_loop_step_end",
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
-    "rcg_register_system", "rcg_rtc_version", "rcg_system_info",
+    "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
 ]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
@@ -183,6 +184,8 @@ def lib():
         "rcg_register_system": (C.c_int, [C.c_char_p, C.c_char_p, i32, i32, i32, C.POINTER(i32)]),
         "rcg_rtc_version": (C.c_int, [C.POINTER(i32), C.POINTER(i32)]),
         "rcg_system_info": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "rcg_system_output_info": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "rcg_out": (C.c_int, [vp, vp, vp, i32]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not export what rcg.h declares
@@ -206,9 +209,11 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac"}``: the id to put in ``rcg_cfg.sys_id`` (>= SYS_USER_BASE), the wall
-    time of the call, the runtime compiler's version and whether the policy has ``jac_T`` (the on-device optimiser).  ``SYS_DIMS`` learns the new id.  Raises NativeError (BAD_ARG with the compiler's
-    log, UNSUPPORTED beyond the dimension limits)."""
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac"}``: the id to put in ``rcg_cfg.sys_id``
+    (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
+    optimiser), its dim_output ``DY`` and whether it defines the output map ``out`` and its adjoint ``out_jac_T``.  ``SYS_DIMS``
+    (``(ds, du, np)``) and ``SYS_DY`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
+    the dimension limits)."""
     import time
 
     L = lib()
@@ -221,4 +226,13 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     check(L.rcg_rtc_version(C.byref(a), C.byref(b)))
     jac = C.c_int32(0)
     check(L.rcg_system_info(sid.value, None, None, None, C.byref(jac)))
-    return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value)}
+    dy, has_out, has_out_jac = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    check(L.rcg_system_output_info(sid.value, C.byref(dy), C.byref(has_out), C.byref(has_out_jac)))
+    SYS_DY[sid.value] = dy.value
+    return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
+            "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value)}
+
+
+def sys_dy(sys_id: int) -> int:
+    """dim_output of a system: its state's dimension unless a registered policy declares an output map with another DY."""
+    return SYS_DY.get(int(sys_id), SYS_DIMS[int(sys_id)][0])

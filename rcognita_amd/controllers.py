@@ -68,17 +68,19 @@ class CtrlOptPred:
                 "run on the native path and there is no CPU fallback")
         self.sys = sys_obj
         # a system compiled at run time (System.hip_policy) runs MPC: no critic kernels, no device search, the optimiser only
-        # when the policy has jac_T
+        # when the policy has jac_T (and out_jac_T, if it has an output map)
         info = type(sys_obj)._hip_info if type(sys_obj).hip_policy is not None else None
         self._runtime_sys = info is not None
         if info is not None:
             if mode != "MPC":
                 raise NotImplementedError(f"{type(sys_obj).__name__} is compiled from hip_policy: mode {mode!r} needs the critic "
                                           "kernels, which exist for the built-in systems only; use mode='MPC'")
-            if candidates is None and (actor_opt == "sampling" or not info["has_jac"]):
+            has_opt = info["has_jac"] and (not info.get("has_out") or info.get("has_out_jac"))
+            if candidates is None and (actor_opt == "sampling" or not has_opt):
                 raise NotImplementedError(
                     f"{type(sys_obj).__name__} is compiled from hip_policy: the device search (actor_opt='sampling') is not "
-                    "available for it, and the on-device optimiser needs jac_T in the policy; pass candidates=")
+                    "available for it, and the on-device optimiser needs jac_T in the policy (and out_jac_T with an output "
+                    "map out); pass candidates=")
         self.dim_input, self.dim_output = dim_input, dim_output
         self.mode = mode
         self.ctrl_clock = t0
@@ -284,13 +286,13 @@ class CtrlOptPred:
                 self._fused_dirty = True
                 return None
             if self._fused_dirty:
-                self._fused_sync(np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self.dim_output])
+                self._fused_sync(np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self._eng_raw.ds])
             res = self._eng_raw.loop_step(act, step, sim.n_substeps, decide=tick, push=push, fit=fit, iters=self.opt_iters)
         st, a, stage, bj, w = res
         stb = st.tobytes()
         if tick:  # what compute_action must be asked with for the decision to be the one it would make: the new state as the
             # observation, the state before the step (the simulator still holds it) as state_sys
-            xsb = np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self.dim_output].tobytes()
+            xsb = np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self._eng_raw.ds].tobytes()
             self._fz = dict(t=t_new, obs=stb, xs=xsb, tick=True, fit=fit, action=a, J=bj, w=w)
             self._stage_last = (stb, a.tobytes(), stage)
         else:
@@ -402,7 +404,7 @@ class CtrlOptPred:
         a = np.broadcast_to(a, (self.B,) + a.shape[1:]).reshape(self.B, -1, self.Nactor, self.dim_input)
         w = self._b(self.w_critic, self.dim_critic) if self.mode != "MPC" else None
         J = self._eng.actor_cost(a, obs=self._b(observation, self.dim_output),
-                                 state_sys=self._b(self.state_sys, self.dim_output), w=w).astype(float)
+                                 state_sys=self._b(self.state_sys, self._eng_raw.ds), w=w).astype(float)
         if single:
             return J[:, 0] if self._batched else float(J[0, 0])
         return J if self._batched else J[0]
@@ -412,7 +414,7 @@ class CtrlOptPred:
         """Replacement of rcognita/controllers.py:1330-1427.  Returns the first action of the best sequence.  Every
         variant decides on the device; like the reference, every call starts from ``action_sqn_init``."""
         obs = self._b(observation, self.dim_output)
-        xs = self._b(self.state_sys, self.dim_output)
+        xs = self._b(self.state_sys, self._eng_raw.ds)
         if self.mode != "MPC":
             self._eng.set_field(N.FIELD_W_CRITIC, self._b(self.w_critic, self.dim_critic))
         if self.candidates is not None:
@@ -446,7 +448,7 @@ class CtrlOptPred:
         if time_in_sample >= self.sampling_time * (1 - self.clock_tol):  # new sample
             if (fz is not None and fz["tick"] and fz["t"] == t
                     and np.ascontiguousarray(self._b(observation, self.dim_output)).tobytes() == fz["obs"]
-                    and np.ascontiguousarray(self._b(self.state_sys, self.dim_output)).tobytes() == fz["xs"]):
+                    and np.ascontiguousarray(self._b(self.state_sys, self._eng_raw.ds)).tobytes() == fz["xs"]):
                 return self._take_fused(t, observation, fz)
             self._fused_dirty = True  # the separate calls below use the handle's fields as scratch (and fz, if any, was for other inputs)
             self.ctrl_clock = t

@@ -134,7 +134,8 @@ __host__ __device__ constexpr int dma_rpl(int r, int esz) { return r * esz <= 24
 
 template <typename Sys, typename real, int R, bool TGT, int V>
 __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, NP = Sys::NP;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, NP = Sys::NP;
+  constexpr bool OUT = HasOut<Sys>::value;  // an output map (registered systems only); else y = x
   constexpr bool G1 = V == DMA_MPC_G1, SQL = dma_is_sql(V), RQL = dma_is_rql(V), CRIT = RQL || SQL;
   constexpr bool GEND = V == DMA_MPC_GEND, GENF = V == DMA_MPC_GENF, GEN = GEND || GENF;
   constexpr bool GENR = V >= DMA_RQL_GEN_0;  // RQL whose stage cost is not the presets' diagonal quadratic one: stage_any per step
@@ -215,7 +216,8 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   // env state: `n`-suffixed = requested one tile ahead for the next env.  Loads only, no
   // "pointer ? load : default" selects (a default written into a register with a load in flight would force a
   // vmcnt(0) on the spot).
-  real y0[DS], yn[DS], x0[DS], xn[DS], pv[NP > 0 ? NP : 1], pn[NP > 0 ? NP : 1], wc[WREG], wn[WREG];
+  // (yn: the observation input as stored - [DY], or a state under obs_x - y0 = obs_of_raw(yn) when the env is adopted)
+  real y0[DY], yn[sys_dxy<Sys>()], x0[DS], xn[DS], pv[NP > 0 ? NP : 1], pn[NP > 0 ? NP : 1], wc[WREG], wn[WREG];
   real wnl = 0;  // (WLDS) weight `lane` of the next env
   const bool lag = A.state_sys != A.obs;  // wave-uniform: a second state vector per env (20 B more per 20 KB of rows)
 #pragma unroll
@@ -226,11 +228,17 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   auto fetch_env = [&](long b) {
     if (RCG_DBG(A, 4)) {  // development: no env-state loads
 #pragma unroll
-      for (int c = 0; c < DS; ++c) yn[c] = xn[c] = (real)0.5;
+      for (int c = 0; c < sys_dxy<Sys>(); ++c) yn[c] = (real)0.5;
+#pragma unroll
+      for (int c = 0; c < DS; ++c) xn[c] = (real)0.5;
       return;
     }
+    if constexpr (OUT) {
+      load_obs_raw<Sys, real>(A.obs, A.obs_x, B, b, yn);
+    } else {
 #pragma unroll
-    for (int c = 0; c < DS; ++c) yn[c] = A.obs[(long)c * B + b];
+      for (int c = 0; c < DS; ++c) yn[c] = A.obs[(long)c * B + b];
+    }
     if (lag) {
 #pragma unroll
       for (int c = 0; c < DS; ++c) xn[c] = A.state_sys[(long)c * B + b];
@@ -312,14 +320,20 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 
   for (int g = 0; g < n_tiles; ++g) {
     if (t == 0) {  // first tile of env b: adopt the state requested one tile ago
+      if constexpr (OUT) {
 #pragma unroll
-      for (int c = 0; c < DS; ++c) {
-        y0[c] = yn[c];
-        x0[c] = lag ? xn[c] : yn[c];
+        for (int c = 0; c < DS; ++c) x0[c] = lag ? xn[c] : yn[c];
+      } else {
+#pragma unroll
+        for (int c = 0; c < DS; ++c) {
+          y0[c] = yn[c];
+          x0[c] = lag ? xn[c] : yn[c];
+        }
       }
 #pragma unroll
       for (int i = 0; i < NP; ++i) pv[i] = pn[i];
       pre_env = Sys::template prepare<real>(pv);
+      if constexpr (OUT) obs_of_raw<Sys, real>(pre_env, A.obs_x, yn, y0);
       if (CRIT && WLDS) {  // the previous env's rollouts are done (program order): its weights may be overwritten
         if (lane < dc_rt) wl[lane] = wnl;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -357,11 +371,18 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
       const real* const cur = rows[j];
-      real x[DS], y[DS];
+      real x[DS], y[DY];
+      if constexpr (OUT) {
 #pragma unroll
-      for (int c = 0; c < DS; ++c) {
-        x[c] = x0[c];  // state_sys
-        y[c] = y0[c];  // observation_sqn[0] = observation
+        for (int c = 0; c < DS; ++c) x[c] = x0[c];  // state_sys
+#pragma unroll
+        for (int c = 0; c < DY; ++c) y[c] = y0[c];  // observation_sqn[0] = observation
+      } else {
+#pragma unroll
+        for (int c = 0; c < DS; ++c) {
+          x[c] = x0[c];  // state_sys
+          y[c] = y0[c];  // observation_sqn[0] = observation
+        }
       }
       real J = 0, gk = 1;
       real S[NCHI];
@@ -383,21 +404,22 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 #pragma unroll
             for (int c = 0; c < DS; ++c) {
               x[c] = fma_r(h, d[c], x[c]);
-              y[c] = x[c];  // sys_out is the identity
+              if constexpr (!OUT) y[c] = x[c];  // no output map: y = x
             }
+            if constexpr (OUT) sys_out<Sys, real, true>(pre_env, x, y);  // observation_sqn[k] = sys_out(state)
           }
           real chi[NCHI];
 #pragma unroll
-          for (int c = 0; c < DS; ++c) chi[c] = TGT ? y[c] - P.target[c] : y[c];
+          for (int c = 0; c < DY; ++c) chi[c] = TGT ? y[c] - P.target[c] : y[c];
 #pragma unroll
-          for (int c = 0; c < DU; ++c) chi[DS + c] = cur[kk * DU + c];
+          for (int c = 0; c < DU; ++c) chi[DY + c] = cur[kk * DU + c];
           if (G1) {
 #pragma unroll
             for (int i = 0; i < NCHI; ++i) S[i] = fma_r(chi[i], chi[i], S[i]);
           } else if (SQL) {
-            critic_phi_accum<DS, DU, real>(chi, y, &cur[kk * DU], Phi, CS);
+            critic_phi_accum<DY, DU, real>(chi, y, &cur[kk * DU], Phi, CS);
           } else if (RQL && kk == N - 1) {
-            J += critic_with<DS, DU, real>(chi, y, &cur[kk * DU], wget, CS);
+            J += critic_with<DY, DU, real>(chi, y, &cur[kk * DU], wget, CS);
           } else if (GEN || GENR) {
             J = fma_r(gk, gen_stage(chi), J);
             gk *= P.gamma;
@@ -462,9 +484,9 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
       if (A.accum) {  // upd_accum_obj (controllers.py:1086-1093), wave-uniform
         real chi[NCHI];
 #pragma unroll
-        for (int c = 0; c < DS; ++c) chi[c] = TGT ? y0[c] - P.target[c] : y0[c];
+        for (int c = 0; c < DY; ++c) chi[c] = TGT ? y0[c] - P.target[c] : y0[c];
 #pragma unroll
-        for (int c = 0; c < DU; ++c) chi[DS + c] = bu[c];
+        for (int c = 0; c < DU; ++c) chi[DY + c] = bu[c];
         // (SQL has no stage cost inside the rollout, so its instances serve ANY stage structure: only upd_accum_obj sees it)
         acc_inc = ((GEN || GENR || SQL) ? stage_any<NCHI, real>(P, chi) : stage_diag<NCHI, real>(P, chi)) * P.sampling_time;
       }

@@ -71,7 +71,8 @@ __host__ __device__ constexpr bool packed_critic_ok(int dc, int esz) { return dc
 
 template <typename Sys, typename real, int R, bool TGT, int V>
 __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> A, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, NP = Sys::NP;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, NP = Sys::NP;
+  constexpr bool OUT = HasOut<Sys>::value;  // an output map (registered systems only); else y = x
   constexpr bool G1 = V == DMA_MPC_G1, SQL = V >= DMA_SQL_0, RQL = V >= DMA_RQL_0 && !SQL, CRIT = RQL || SQL;
   constexpr int CS = SQL ? V - DMA_SQL_0 : (RQL ? V - DMA_RQL_0 : 0);  // compile-time critic structure
   constexpr int DC = CRIT ? dma_dc(CS, DS, DU) : 1;
@@ -128,10 +129,19 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
   // the dispatch gap behind it: 3 us of a 14-20 us tick at K = 8 .. 16.
   const bool fused = A.sim_n_sub > 0;  // wave-uniform
   real* const sst = reinterpret_cast<real*>(smem_raw + (size_t)4 * TILE) + (size_t)wave_in_wg * (2 * DS * 64);
-  real y0[DS], yn[DS], x0[DS], xn[DS], pn[NP > 0 ? NP : 1];
+  // (yn: the observation input as stored - [DY], or a state under obs_x, as the fused env step's new states always are -
+  // y0 = obs_of_raw(yn) when the tile is adopted)
+  real y0[DY], yn[sys_dxy<Sys>()], x0[DS], xn[DS], pn[NP > 0 ? NP : 1];
   const bool lag = A.state_sys != A.obs;  // wave-uniform
+  if constexpr (OUT) {
 #pragma unroll
-  for (int c = 0; c < DS; ++c) yn[c] = xn[c] = 0;
+    for (int c = 0; c < sys_dxy<Sys>(); ++c) yn[c] = 0;
+#pragma unroll
+    for (int c = 0; c < DS; ++c) xn[c] = 0;
+  } else {
+#pragma unroll
+    for (int c = 0; c < DS; ++c) yn[c] = xn[c] = 0;
+  }
 #pragma unroll
   for (int i = 0; i < NP; ++i) pn[i] = P.pars[i];
   auto fetch_env = [&](int j) {  // the state of MY env of tile j (lanes without a row request nothing)
@@ -145,8 +155,12 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
           xn[c] = sst[(DS + c) * 64 + el];
         }
       } else {
+        if constexpr (OUT) {
+          load_obs_raw<Sys, real>(A.obs, A.obs_x, B, b, yn);
+        } else {
 #pragma unroll
-        for (int c = 0; c < DS; ++c) yn[c] = A.obs[(long)c * B + b];
+          for (int c = 0; c < DS; ++c) yn[c] = A.obs[(long)c * B + b];
+        }
         if (lag) {
 #pragma unroll
           for (int c = 0; c < DS; ++c) xn[c] = A.state_sys[(long)c * B + b];
@@ -213,12 +227,19 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
 
   for (int j = 0; j < n_tiles; ++j) {
     const int ne = envs_in(j);
+    if constexpr (OUT) {
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      y0[c] = yn[c];
-      x0[c] = lag ? xn[c] : yn[c];
+      for (int c = 0; c < DS; ++c) x0[c] = lag ? xn[c] : yn[c];
+      if (A.pars_env) pre_env = Sys::template prepare<real>(pn);
+      obs_of_raw<Sys, real>(pre_env, A.obs_x, yn, y0);
+    } else {
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        y0[c] = yn[c];
+        x0[c] = lag ? xn[c] : yn[c];
+      }
+      if (A.pars_env) pre_env = Sys::template prepare<real>(pn);
     }
-    if (A.pars_env) pre_env = Sys::template prepare<real>(pn);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // tile j has landed
     real cur[R];
     {
@@ -240,11 +261,18 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
     }
 
     // _actor_cost of my row (controllers.py:1284-1326): k_actor_dma's rollout, registers only
-    real x[DS], y[DS];
+    real x[DS], y[DY];
+    if constexpr (OUT) {
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      x[c] = x0[c];
-      y[c] = y0[c];
+      for (int c = 0; c < DS; ++c) x[c] = x0[c];
+#pragma unroll
+      for (int c = 0; c < DY; ++c) y[c] = y0[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        x[c] = x0[c];
+        y[c] = y0[c];
+      }
     }
     real J = 0, gk = 1;
     real S[NCHI];
@@ -262,21 +290,22 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
 #pragma unroll
         for (int c = 0; c < DS; ++c) {
           x[c] = fma_r(h, d[c], x[c]);
-          y[c] = x[c];
+          if constexpr (!OUT) y[c] = x[c];
         }
+        if constexpr (OUT) sys_out<Sys, real, true>(pre_env, x, y);
       }
       real chi[NCHI];
 #pragma unroll
-      for (int c = 0; c < DS; ++c) chi[c] = TGT ? y[c] - P.target[c] : y[c];
+      for (int c = 0; c < DY; ++c) chi[c] = TGT ? y[c] - P.target[c] : y[c];
 #pragma unroll
-      for (int c = 0; c < DU; ++c) chi[DS + c] = cur[kk * DU + c];
+      for (int c = 0; c < DU; ++c) chi[DY + c] = cur[kk * DU + c];
       if (G1) {
 #pragma unroll
         for (int i = 0; i < NCHI; ++i) S[i] = fma_r(chi[i], chi[i], S[i]);
       } else if (SQL) {
-        critic_phi_accum<DS, DU, real>(chi, y, &cur[kk * DU], Phi, CS);
+        critic_phi_accum<DY, DU, real>(chi, y, &cur[kk * DU], Phi, CS);
       } else if (RQL && kk == N - 1) {
-        J += critic_with<DS, DU, real>(chi, y, &cur[kk * DU], wget, CS);
+        J += critic_with<DY, DU, real>(chi, y, &cur[kk * DU], wget, CS);
       } else {
         J = fma_r(gk, stage_diag<NCHI, real>(P, chi), J);
         gk *= P.gamma;
@@ -320,18 +349,18 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
     const real pJ = __shfl(segJ, src0, 64);
     const int pI = __shfl(segI, src0, 64);
     const int wl = parks ? gi * K + pI : lane;     // the winner's lane
-    real bu[DU], yw[DS];
+    real bu[DU], yw[DY];
 #pragma unroll
     for (int c = 0; c < DU; ++c) bu[c] = __shfl(cur[c], wl, 64);  // the sequence's first action
     real acc_inc = 0;
     if (A.accum) {  // upd_accum_obj (controllers.py:1086-1093) at the env's observation (every lane of the env holds it)
 #pragma unroll
-      for (int c = 0; c < DS; ++c) yw[c] = __shfl(y0[c], src0, 64);
+      for (int c = 0; c < DY; ++c) yw[c] = __shfl(y0[c], src0, 64);
       real chi[NCHI];
 #pragma unroll
-      for (int c = 0; c < DS; ++c) chi[c] = TGT ? yw[c] - P.target[c] : yw[c];
+      for (int c = 0; c < DY; ++c) chi[c] = TGT ? yw[c] - P.target[c] : yw[c];
 #pragma unroll
-      for (int c = 0; c < DU; ++c) chi[DS + c] = bu[c];
+      for (int c = 0; c < DU; ++c) chi[DY + c] = bu[c];
       acc_inc = stage_diag<NCHI, real>(P, chi) * P.sampling_time;
     }
     if (parks) {

@@ -100,7 +100,7 @@ __device__ __forceinline__ real opt_quad_max(real x) {
 
 template <typename real>
 struct OptArgs {
-  const real* obs;        // [dy][B]
+  const real* obs;        // [dy][B], or [ds][B] (obs_x: y_0 = out(obs), ActorArgs)
   const real* state_sys;  // [ds][B]
   const real* pars_env;   // [np][B] or nullptr
   const real* w;          // [dc][B] critic weights (RQL / SQL) or nullptr
@@ -118,6 +118,7 @@ struct OptArgs {
   int dcw;                // critic weights staged in LDS per env (dc for RQL / SQL, else 0)
   real ftol;              // an env is done after an accepted step that lowered J by <= ftol (rcg_set_optimizer_tol; 0: never)
   LoopArgs<real> loop;    // LOOP instances only (rcg_loop_step): the loop iteration's head and tail around the decision
+  int obs_x;              // as ActorArgs::obs_x (a system with an output map only)
 };
 
 __device__ __forceinline__ void wave_lds_sync() {
@@ -126,10 +127,10 @@ __device__ __forceinline__ void wave_lds_sync() {
 }
 
 // reals of LDS one wave needs (host and device agree through this one function):
-// u [G][R] | d [G][R] (= q, the two-loop work vector) | X [N*DS][G] | y0 [DS][G] | xs [DS][G] | pars [NPS][G] | w [DC][G] | g [R][G] |
+// u [G][R] | d [G][R] (= q, the two-loop work vector) | X [N*DS][G] | y0 [DY][G] | xs [DS][G] | pars [NPS][G] | w [DC][G] | g [R][G] |
 // S [M][R][G] | Y [M][R][G] | gamma^k [N]
-__host__ __device__ constexpr int opt_lds_reals(int N, int DS, int DU, int NP, int DC, int M) {
-  return OPT_G * (2 * N * DU + N * DS + 2 * DS + (NP > 0 ? NP : 1) + DC + N * DU + 2 * M * N * DU) + N;
+__host__ __device__ constexpr int opt_lds_reals(int N, int DS, int DU, int NP, int DC, int M, int DY) {
+  return OPT_G * (2 * N * DU + N * DS + DY + DS + (NP > 0 ? NP : 1) + DC + N * DU + 2 * M * N * DU) + N;
 }
 
 // gk * d rho / d chi of stage_obj (controllers.py:1076-1082): quadratic chi R1 chi -> (R1 + R1^T) chi;
@@ -228,7 +229,9 @@ __device__ __forceinline__ void critic_grad_with(const real* chi, const real* y,
 // decided action, the row and the sequence number into the pinned host buffer).  Same device functions as the three launches.
 template <typename Sys, typename real, bool TGT, bool GENERIC, bool PAIRS, bool LOOP = false>
 __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, NP = Sys::NP, NPS = NP > 0 ? NP : 1, G = OPT_G;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, NP = Sys::NP, NPS = NP > 0 ? NP : 1, G = OPT_G;
+  constexpr bool OUT = HasOut<Sys>::value;
+  static_assert(!(OUT && LOOP), "rcg_loop_step serves the built-in systems only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
   const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -239,11 +242,11 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
   const int ng = (int)((B - b0) < G ? (B - b0) : G);  // envs of this wave (wave-uniform)
   const int N = P.n_actor, R = N * DU;
   const int M = PAIRS ? A.memory : 0, DCW = A.dcw;
-  real* const su = reinterpret_cast<real*>(smem_raw) + (size_t)wave_in_wg * opt_lds_reals(N, DS, DU, NP, DCW, M);
+  real* const su = reinterpret_cast<real*>(smem_raw) + (size_t)wave_in_wg * opt_lds_reals(N, DS, DU, NP, DCW, M, DY);
   real* const sd = su + G * R;
   real* const sX = sd + G * R;
   real* const sY = sX + N * DS * G;
-  real* const sS = sY + DS * G;
+  real* const sS = sY + DY * G;
   real* const sP = sS + DS * G;
   real* const sW = sP + NPS * G;    // critic weights [DCW][G]
   real* const sGc = sW + DCW * G;   // current gradient [R][G]
@@ -255,7 +258,7 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
 
   const bool mine = lane < ng;       // lane == env view
   const long be = b0 + (mine ? lane : 0);
-  real y0e[DS], xse[DS], pve[NPS], w[DU], w2[DU];
+  real y0e[DY], xse[DS], pve[NPS], w[DU], w2[DU], on[sys_dxy<Sys>()];
   if constexpr (LOOP) {
     real ul[DU];
     if (mine) {
@@ -265,15 +268,22 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
       for (int c = 0; c < DS; ++c) y0e[c] = xse[c] = (real)0;  // an idle lane stands for no env (its values are never used)
     }
   } else {
+    if constexpr (OUT) {
+      load_obs_raw<Sys, real>(A.obs, A.obs_x, B, be, on);
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      y0e[c] = A.obs[(long)c * B + be];
-      xse[c] = A.state_sys[(long)c * B + be];
+      for (int c = 0; c < DS; ++c) xse[c] = A.state_sys[(long)c * B + be];
+    } else {  // (no output map: the statements in their earlier order)
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        y0e[c] = A.obs[(long)c * B + be];
+        xse[c] = A.state_sys[(long)c * B + be];
+      }
     }
   }
 #pragma unroll
   for (int i = 0; i < NP; ++i) pve[i] = A.pars_env ? A.pars_env[(long)i * B + be] : P.pars[i];
   const auto pre_e = Sys::template prepare<real>(pve);
+  if constexpr (OUT) obs_of_raw<Sys, real>(pre_e, A.obs_x, on, y0e);
 #pragma unroll
   for (int c = 0; c < DU; ++c) {
     w[c] = P.hi[c] - P.lo[c];
@@ -281,10 +291,17 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
   }
   const real h = P.h_pred;
   if (lane < G) {  // the env data once more in LDS: phase 2 needs env e's values wave-uniformly
+    if constexpr (OUT) {
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      sY[c * G + lane] = y0e[c];
-      sS[c * G + lane] = xse[c];
+      for (int c = 0; c < DY; ++c) sY[c * G + lane] = y0e[c];
+#pragma unroll
+      for (int c = 0; c < DS; ++c) sS[c * G + lane] = xse[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        sY[c * G + lane] = y0e[c];
+        sS[c * G + lane] = xse[c];
+      }
     }
 #pragma unroll
     for (int i = 0; i < NP; ++i) sP[i * G + lane] = pve[i];
@@ -321,11 +338,18 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
   // the env the caller stands for
   auto cost_of = [&](const real* ue, const real* de, const real* y0, const real* xs,
                      const typename Sys::template Pre<real>& pre, real alpha, auto wg) -> real {
-    real x[DS], y[DS], up[DU];
+    real x[DS], y[DY], up[DU];
+    if constexpr (OUT) {
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      x[c] = xs[c];
-      y[c] = y0[c];
+      for (int c = 0; c < DS; ++c) x[c] = xs[c];
+#pragma unroll
+      for (int c = 0; c < DY; ++c) y[c] = y0[c];
+    } else {
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        x[c] = xs[c];
+        y[c] = y0[c];
+      }
     }
 #pragma unroll
     for (int c = 0; c < DU; ++c) up[c] = 0;
@@ -346,11 +370,12 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
 #pragma unroll
         for (int c = 0; c < DS; ++c) {
           x[c] = fma_r(h, d[c], x[c]);
-          y[c] = x[c];
+          if constexpr (!OUT) y[c] = x[c];
         }
+        if constexpr (OUT) sys_out<Sys, real, true>(pre, x, y);
       }
       real chi[NCHI];
-      make_chi<DS, DU, TGT, real>(P, y, u, chi);
+      make_chi<DY, DU, TGT, real>(P, y, u, chi);
       if (!GENERIC) {
         if (g1) {  // wave-uniform
 #pragma unroll
@@ -359,7 +384,7 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
           J = fma_r(sg[k], stage_diag<NCHI, real>(P, chi), J);
         }
       } else if (mode == RCG_MODE_SQL || (mode == RCG_MODE_RQL && k == N - 1)) {  // wave-uniform
-        J += critic_with<DS, DU, real>(chi, y, u, wg, cs);
+        J += critic_with<DY, DU, real>(chi, y, u, wg, cs);
       } else {
         J = fma_r(sg[k], stage_with<NCHI, real>(P, chi, sk), J);
       }
@@ -411,30 +436,36 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
       for (int c = 0; c < DS; ++c) lam[c] = 0;
       for (int k = N - 1; k >= 0; --k) {
         const real gk = sg[k];
-        real u[DU], xk[DS], g[DU], gy[DS];
+        real u[DU], xk[DS], g[DU], gy[DY], yo[DY];
 #pragma unroll
         for (int c = 0; c < DU; ++c) u[c] = ue[k * DU + c];
 #pragma unroll
         for (int c = 0; c < DS; ++c) xk[c] = (k >= 1) ? sX[(k * DS + c) * G + lane] : xse[c];
+        if constexpr (OUT) {  // y_k = out(x_k) as the forward pass forms it (k >= 1; only those terms reach lam)
+          sys_out<Sys, real, true>(pre_e, xk, yo);
+        } else {
+#pragma unroll
+          for (int c = 0; c < DY; ++c) yo[c] = xk[c];
+        }
         if (!GENERIC) {
 #pragma unroll
-          for (int c = 0; c < DU; ++c) g[c] = gk * (real)2 * P.R1d[DS + c] * u[c];
+          for (int c = 0; c < DU; ++c) g[c] = gk * (real)2 * P.R1d[DY + c] * u[c];
 #pragma unroll
-          for (int c = 0; c < DS; ++c) gy[c] = gk * (real)2 * P.R1d[c] * (TGT ? xk[c] - P.target[c] : xk[c]);
+          for (int c = 0; c < DY; ++c) gy[c] = gk * (real)2 * P.R1d[c] * (TGT ? yo[c] - P.target[c] : yo[c]);
         } else {
-          real yk[DS], chi[NCHI];
+          real yk[DY], chi[NCHI];
 #pragma unroll
-          for (int c = 0; c < DS; ++c) yk[c] = (k >= 1) ? xk[c] : y0e[c];  // y_0 is the observation
-          make_chi<DS, DU, TGT, real>(P, yk, u, chi);
+          for (int c = 0; c < DY; ++c) yk[c] = (k >= 1) ? yo[c] : y0e[c];  // y_0 is the observation
+          make_chi<DY, DU, TGT, real>(P, yk, u, chi);
           if (mode == RCG_MODE_SQL || (mode == RCG_MODE_RQL && k == N - 1)) {  // wave-uniform
-            critic_grad_with<DS, DU, real>(chi, yk, u, w_mine, cs, gy, g);
+            critic_grad_with<DY, DU, real>(chi, yk, u, w_mine, cs, gy, g);
           } else {
             real gc[NCHI];
             stage_grad_with<NCHI, real>(P, chi, sk, gk, gc);
 #pragma unroll
-            for (int c = 0; c < DS; ++c) gy[c] = gc[c];
+            for (int c = 0; c < DY; ++c) gy[c] = gc[c];
 #pragma unroll
-            for (int c = 0; c < DU; ++c) g[c] = gc[DS + c];
+            for (int c = 0; c < DU; ++c) g[c] = gc[DY + c];
           }
         }
         real lamk[DS];
@@ -450,8 +481,15 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
           for (int c = 0; c < DS; ++c) lamk[c] = 0;
         }
         if (k >= 1) {  // y_0 is the observation, not a function of the actions
+          if constexpr (OUT) {  // d c_k / d x_k = (d out / d x)^T d c_k / d y_k
+            real gx[DS];
+            Sys::template out_jac_T<real, true>(pre_e, xk, gy, gx);
 #pragma unroll
-          for (int c = 0; c < DS; ++c) lamk[c] += gy[c];
+            for (int c = 0; c < DS; ++c) lamk[c] += gx[c];
+          } else {
+#pragma unroll
+            for (int c = 0; c < DS; ++c) lamk[c] += gy[c];
+          }
         }
 #pragma unroll
         for (int c = 0; c < DS; ++c) lam[c] = lamk[c];
@@ -609,11 +647,18 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
       const real Jinc_e = __shfl(Jinc, es, 64);
       const int quasi_e = __shfl((int)quasi, es, 64);
       const int head_e = __shfl(head, es, 64);
-      real y0[DS], xs[DS], pv[NPS];
+      real y0[DY], xs[DS], pv[NPS];
+      if constexpr (OUT) {
 #pragma unroll
-      for (int c = 0; c < DS; ++c) {
-        y0[c] = sY[c * G + es];
-        xs[c] = sS[c * G + es];
+        for (int c = 0; c < DY; ++c) y0[c] = sY[c * G + es];
+#pragma unroll
+        for (int c = 0; c < DS; ++c) xs[c] = sS[c * G + es];
+      } else {
+#pragma unroll
+        for (int c = 0; c < DS; ++c) {
+          y0[c] = sY[c * G + es];
+          xs[c] = sS[c * G + es];
+        }
       }
 #pragma unroll
       for (int i = 0; i < NP; ++i) pv[i] = sP[i * G + es];

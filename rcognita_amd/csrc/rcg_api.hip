@@ -128,7 +128,7 @@ static void build_params(const rcg_handle* h, KParams<real>* P, real* rfull_host
     P->R1d[i] = (real)c.R1[i * n + i];
     P->R2d[i] = biq ? (real)c.R2[i * n + i] : (real)0;
   }
-  for (int i = 0; i < h->ds; ++i) P->target[i] = (c.flags & RCG_FLAG_HAS_TARGET) ? (real)c.target[i] : (real)0;
+  for (int i = 0; i < h->dy; ++i) P->target[i] = (c.flags & RCG_FLAG_HAS_TARGET) ? (real)c.target[i] : (real)0;
   P->gamma = (real)c.gamma;
   P->h_pred = (real)c.pred_step_size;
   P->dt_sim = (real)c.dt_sim;
@@ -176,15 +176,27 @@ int rcg_version(void) { return RCG_VERSION; }
 const char* rcg_last_error(const rcg_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32_t* has_jac) {
-  RtcDims d{0, 0, 0, true};
+  RtcDims d{0, 0, 0, true, 0, false, false};
   if (sys_id >= 0 && sys_id <= 2)
-    d = RtcDims{kDims[sys_id][0], kDims[sys_id][1], kDims[sys_id][2], true};
+    d = RtcDims{kDims[sys_id][0], kDims[sys_id][1], kDims[sys_id][2], true, kDims[sys_id][0], false, false};
   else if (!(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_info: bad sys_id %d", sys_id);
   if (ds) *ds = d.ds;
   if (du) *du = d.du;
   if (np) *np = d.np;
   if (has_jac) *has_jac = d.has_jac ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_output_info(int32_t sys_id, int32_t* dy, int32_t* has_out, int32_t* has_out_jac) {
+  RtcDims d{0, 0, 0, false, 0, false, false};
+  if (sys_id >= 0 && sys_id <= 2)
+    d.dy = kDims[sys_id][0];  // the built-in systems observe their state
+  else if (!(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_output_info: bad sys_id %d", sys_id);
+  if (dy) *dy = d.dy;
+  if (has_out) *has_out = d.has_out ? 1 : 0;
+  if (has_out_jac) *has_out_jac = d.has_out_jac ? 1 : 0;
   return RCG_OK;
 }
 
@@ -201,7 +213,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: struct_size %d != sizeof(rcg_cfg) %zu (ABI mismatch)",
                     cfg->struct_size, sizeof(rcg_cfg));
   // a built-in system, or one registered at run time (rcg_rtc.hip: its dimensions come from the registry)
-  RtcDims rd{0, 0, 0, false};
+  RtcDims rd{0, 0, 0, false, 0, false, false};
   const RtcSystem* rtc = cfg->sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(cfg->sys_id, &rd) : nullptr;
   if ((cfg->sys_id < 0 || cfg->sys_id > 2) && !rtc)
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad sys_id %d", cfg->sys_id);
@@ -245,8 +257,10 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->ds = ds;
   h->du = du;
   h->np = np;
-  h->nchi = ds + du;
-  h->dc = dim_critic(cfg->critic_struct, ds, du);
+  h->rtc_has_out = rtc && rd.has_out;
+  h->dy = rtc ? rd.dy : ds;  // R1 / R2 are (dy + du)^2 and the target has dy entries
+  h->nchi = h->dy + du;
+  h->dc = dim_critic(cfg->critic_struct, h->dy, du);  // the critic's regressor is over [y, u] (controllers.py:1192-1214)
   h->esz = cfg->dtype == RCG_F64 ? 8 : 4;
   h->stream = nullptr;
   h->own_stream = nullptr;
@@ -341,7 +355,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   if (cfg->buffer_size > 0) {
     h->fbytes[RCG_FIELD_W_CRITIC] = h->dc * B * e;
     h->fbytes[RCG_FIELD_W_PREV] = h->dc * B * e;
-    h->fbytes[RCG_FIELD_OBS_BUF] = (size_t)cfg->buffer_size * ds * B * e;
+    h->fbytes[RCG_FIELD_OBS_BUF] = (size_t)cfg->buffer_size * h->dy * B * e;  // observations [buffer_size][dy][B]
     h->fbytes[RCG_FIELD_ACT_BUF] = (size_t)cfg->buffer_size * du * B * e;
   }
   for (int i = 0; i < RCG_FIELD_COUNT_; ++i) {
@@ -597,6 +611,15 @@ int rcg_stage_obj(rcg_handle* h, const void* obs, const void* act, void* out, in
   DeviceGuard dev_guard(h);
   if (!h || !obs || !act || !out || n < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_stage_obj: bad argument");
   return h->sys->stage_obj(h, obs, act, out, n);
+}
+
+int rcg_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
+  DeviceGuard dev_guard(h);
+  if (!h || !state || !obs || n < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_out: bad argument");
+  if (h->rtc && h->rtc_has_out) return rtc_out(h, state, obs, n);
+  // no output map: the observation is the state (systems.py:185)
+  HIPCHK(h, hipMemcpyAsync(obs, state, (size_t)h->ds * n * h->esz, hipMemcpyDeviceToDevice, h->stream));
+  return RCG_OK;
 }
 
 int rcg_critic(rcg_handle* h, const void* obs, const void* act, const void* w, void* out, int32_t n) {

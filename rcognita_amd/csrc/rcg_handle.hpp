@@ -20,6 +20,8 @@
 struct rcg_handle {
   rcg_cfg cfg;
   int ds, du, np, dc, nchi;
+  int dy;      // dim_output: ds, or the DY of a registered system with an output map (nchi = dy + du)
+  bool rtc_has_out;  // a registered system with an output map (rcg_out launches k_out)
   size_t esz;  // sizeof(real)
   hipStream_t stream;
   hipStream_t own_stream;  // created by rcg_use_own_stream, destroyed with the handle (nullptr: none)
@@ -223,12 +225,12 @@ static inline int opt_memory_of(const rcg_handle* h) {
   const bool generic = !(h->cfg.mode == RCG_MODE_MPC && h->p32.stage_kind == 0);
   const int dcw = h->cfg.mode != RCG_MODE_MPC ? h->dc : 0;
   int mem = generic ? 4 : 0;
-  while (mem > 0 && (size_t)rcg::opt_lds_reals(h->cfg.n_actor, h->ds, h->du, h->np, dcw, mem) * h->esz > (size_t)160 * 1024) --mem;
+  while (mem > 0 && (size_t)rcg::opt_lds_reals(h->cfg.n_actor, h->ds, h->du, h->np, dcw, mem, h->dy) * h->esz > (size_t)160 * 1024) --mem;
   return mem;
 }
 static inline size_t opt_wave_lds_bytes(const rcg_handle* h) {
   const int dcw = h->cfg.mode != RCG_MODE_MPC ? h->dc : 0;
-  return (size_t)rcg::opt_lds_reals(h->cfg.n_actor, h->ds, h->du, h->np, dcw, opt_memory_of(h)) * h->esz;
+  return (size_t)rcg::opt_lds_reals(h->cfg.n_actor, h->ds, h->du, h->np, dcw, opt_memory_of(h), h->dy) * h->esz;
 }
 
 static inline unsigned blocks_for(long n, int bs = 256) { return (unsigned)((n + bs - 1) / bs); }
@@ -265,9 +267,14 @@ extern const SysVTable kVt3WRobot, kVt3WRobotNI, kVt2Tank;
 // nullptr for an id nobody registered.  Every such handle shares kVtRtc; the launchers find their system through h->rtc.
 struct RtcDims {
   int ds, du, np;
-  bool has_jac;  // the policy defines jac_T: k_actor_opt is available
+  bool has_jac;      // the policy defines jac_T: k_actor_opt is available
+  int dy;            // dim_output: the policy's DY (default ds)
+  bool has_out;      // the policy defines out (y = out(x)); without it y = x
+  bool has_out_jac;  // ... and out_jac_T, which k_actor_opt needs when there is an output map
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
+// rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])
+int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n);
 extern const SysVTable kVtRtc;
 // sets the thread's error text (rcg_last_error(NULL)) without rcg_fail's length limit: hipRTC's log
 void rcg_set_thread_error(const std::string& text);

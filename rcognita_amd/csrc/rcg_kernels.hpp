@@ -53,6 +53,71 @@ struct KParams {
 };
 
 // ---------------------------------------------------------------------------------------------
+// The output map y = out(x) (systems.py:185: "if not overridden, output is identical to state").  Only a system registered at
+// run time may define one: rcg_rtc.hip's adapter then sets HAS_OUT and DY (dim_output) from the policy.  Every built-in
+// observes its state: for them the helpers below reduce to y = x and DY = DS, chosen with `if constexpr`.  Where a kernel
+// loads or copies y, the branch without an output map keeps the statements in their earlier order, which keeps the built-in
+// instances' register use and scratch as they were.
+template <class...>
+using void_t_ = void;
+template <class S, class = void>
+struct HasOut {
+  static constexpr bool value = false;
+};
+template <class S>
+struct HasOut<S, void_t_<decltype(S::HAS_OUT)>> {
+  static constexpr bool value = S::HAS_OUT;
+};
+template <class S>
+constexpr int sys_dy() {
+  if constexpr (HasOut<S>::value)
+    return S::DY;
+  else
+    return S::DS;
+}
+// registers that hold an observation input: [DY], or a state [DS] when the kernel is handed a state (ActorArgs::obs_x)
+template <class S>
+constexpr int sys_dxy() {
+  return sys_dy<S>() > S::DS ? sys_dy<S>() : S::DS;
+}
+// y = out(x).  HW as in rhs: the Euler rollouts pass true, the observation of a handed-in state (y_0, upd_accum_obj, k_out) false
+template <typename Sys, typename real, bool HW>
+__device__ __forceinline__ void sys_out(const typename Sys::template Pre<real>& q, const real* x, real* y) {
+  if constexpr (HasOut<Sys>::value) {
+    Sys::template out<real, HW>(q, x, y);
+  } else {
+#pragma unroll
+    for (int c = 0; c < Sys::DS; ++c) y[c] = x[c];
+  }
+}
+// the observation input of env b as it is stored: [DY][B], or a state [DS][B] when obs_x (a system with `out` only)
+template <typename Sys, typename real>
+__device__ __forceinline__ void load_obs_raw(const real* obs, int obs_x, long B, long b, real* on) {
+  if constexpr (HasOut<Sys>::value) {
+    const int n = obs_x ? Sys::DS : Sys::DY;  // wave-uniform
+#pragma unroll
+    for (int c = 0; c < sys_dxy<Sys>(); ++c) on[c] = c < n ? obs[(long)c * B + b] : (real)0;
+  } else {
+#pragma unroll
+    for (int c = 0; c < Sys::DS; ++c) on[c] = obs[(long)c * B + b];
+  }
+}
+// y_0 from that input: the observation itself, or out(state)
+template <typename Sys, typename real>
+__device__ __forceinline__ void obs_of_raw(const typename Sys::template Pre<real>& q, int obs_x, const real* on, real* y0) {
+  if constexpr (HasOut<Sys>::value) {
+    if (obs_x) {
+      Sys::template out<real, false>(q, on, y0);
+    } else {
+#pragma unroll
+      for (int c = 0; c < Sys::DY; ++c) y0[c] = on[c];
+    }
+  } else {
+#pragma unroll
+    for (int c = 0; c < Sys::DS; ++c) y0[c] = on[c];
+  }
+}
+
 // chi = [obs - target, act]   (controllers.py:1069-1072, 1200-1203)
 template <int DS, int DU, bool TGT, typename real>
 __device__ __forceinline__ void make_chi(const KParams<real>& P, const real* y, const real* u, real* chi) {
@@ -280,7 +345,7 @@ __device__ __forceinline__ void rk4_step(const typename Sys::template Pre<real>&
 template <typename real>
 struct ActorArgs {
   const real* cand;       // [B][K][N][du], or nullptr: generated level grid
-  const real* obs;        // [dy][B]
+  const real* obs;        // [dy][B], or [ds][B] (obs_x)
   const real* state_sys;  // [ds][B]
   const real* pars_env;   // [np][B] or nullptr
   const real* w;          // [dc][B] (RQL/SQL)
@@ -310,6 +375,9 @@ struct ActorArgs {
   const real* sim_action; // [du][B] the held action
   uint32_t* sim_status;   // [B]
   int sim_n_sub;
+  // (a system with an output map) obs holds a state [ds][B] - the handle's STATE on a tick, or the fused env step's new states -
+  // and y_0 = out(obs); else obs is the observation [dy][B].  Ignored by the instances of the built-in systems (y = x)
+  int obs_x;
 };
 
 typedef float v4f __attribute__((ext_vector_type(4)));  // one 16-B global_load_dwordx4 / ds_write_b128
@@ -372,17 +440,25 @@ template <typename Sys, typename real, bool TGT, bool STREAM, int MODE_C, int SK
 __device__ __forceinline__ real rollout_cost(const KParams<real>& P, const typename Sys::template Pre<real>& pre, int N_rt,
                                              const real* xs, const real* y0, const real* urow, const real* ugen,
                                              WGet wget, real* u0) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
   const int N = NC > 0 ? NC : N_rt;
   const int mode = MODE_C >= 0 ? MODE_C : P.mode;
   const int sk = SK_C >= 0 ? SK_C : P.stage_kind;
   const int cs = CS_C >= 0 ? CS_C : P.critic_struct;
   const real h = P.h_pred;
-  real x[DS], y[DS];
+  constexpr bool OUT = HasOut<Sys>::value;
+  real x[DS], y[DY];
+  if constexpr (OUT) {
 #pragma unroll
-  for (int c = 0; c < DS; ++c) {
-    x[c] = xs[c];
-    y[c] = y0[c];
+    for (int c = 0; c < DS; ++c) x[c] = xs[c];
+#pragma unroll
+    for (int c = 0; c < DY; ++c) y[c] = y0[c];
+  } else {  // (no output map: the statements in their earlier order)
+#pragma unroll
+    for (int c = 0; c < DS; ++c) {
+      x[c] = xs[c];
+      y[c] = y0[c];
+    }
   }
   static_assert(!G1 || ((MODE_C == RCG_MODE_MPC || MODE_C == RCG_MODE_RQL) && SK_C == 0),
                 "the per-component sum is a variant of the diagonal-R1 stage sums (MPC: all N steps, RQL: the first N - 1)");
@@ -392,7 +468,7 @@ __device__ __forceinline__ real rollout_cost(const KParams<real>& P, const typen
 #pragma unroll
   for (int i = 0; i < (G1 ? NCHI : 1); ++i) S[i] = 0;
   constexpr bool SUMF = MODE_C == RCG_MODE_SQL && CS_C >= 0;  // SQL: per-feature sums (critic_phi_accum)
-  constexpr int NPHI = SUMF ? critic_dim<DS, DU>(CS_C >= 0 ? CS_C : 0) : 1;
+  constexpr int NPHI = SUMF ? critic_dim<DY, DU>(CS_C >= 0 ? CS_C : 0) : 1;
   real Phi[NPHI];
 #pragma unroll
   for (int i = 0; i < NPHI; ++i) Phi[i] = 0;
@@ -400,7 +476,7 @@ __device__ __forceinline__ real rollout_cost(const KParams<real>& P, const typen
   for (int c = 0; c < DU; ++c) up[c] = 0;
   real zw0 = 0;  // zero-weighted state components of the observation: 0, or NaN if one of them is not finite (see the end)
 #pragma unroll
-  for (int i = 0; i < DS; ++i)
+  for (int i = 0; i < DY; ++i)
     if (G1 && ((ZW >> i) & 1u)) zw0 = fma_r(P.R1d[i], y0[i] * y0[i], zw0);
 // One step kk of the rollout, expanded below in the runtime-horizon loop and in the fully unrolled compile-time one (a macro,
 // not a lambda: wrapping the body in a lambda changed one fma contraction in one instance, and T ticks in one launch must
@@ -422,28 +498,29 @@ _Pragma("unroll")                                                               
 _Pragma("unroll")                                                                                                        \
       for (int c = 0; c < DS; ++c) {                                                                                  \
         x[c] = fma_r(h, d[c], x[c]);                                                                                  \
-        y[c] = x[c];                                                                                                  \
+        if constexpr (!OUT) y[c] = x[c]; /* no output map: y = x */                                                   \
       }                                                                                                               \
+      if constexpr (OUT) sys_out<Sys, real, true>(pre, x, y);                                                         \
     }                                                                                                                 \
     real chi[NCHI];                                                                                                   \
-    make_chi<DS, DU, TGT, real>(P, y, u, chi);                                                                        \
+    make_chi<DY, DU, TGT, real>(P, y, u, chi);                                                                        \
     if (G1 && (MODE_C == RCG_MODE_MPC || kk < N - 1)) {                                                               \
 _Pragma("unroll")                                                                                                        \
       for (int i = 0; i < NCHI; ++i)                                                                                  \
         if (!((ZW >> i) & 1u)) S[G1 ? i : 0] = fma_r(chi[i], chi[i], S[G1 ? i : 0]);                                  \
     } else if (G1) {                                                                                                  \
-      J += critic_with<DS, DU, real>(chi, y, u, wget, cs);                                                            \
+      J += critic_with<DY, DU, real>(chi, y, u, wget, cs);                                                            \
     } else if (mode == RCG_MODE_MPC) {                                                                                \
       J = fma_r(gk, stage_with<NCHI, real>(P, chi, sk), J);                                                           \
     } else if (mode == RCG_MODE_RQL) {                                                                                \
       if (kk < N - 1)                                                                                                 \
         J = fma_r(gk, stage_with<NCHI, real>(P, chi, sk), J);                                                         \
       else                                                                                                            \
-        J += critic_with<DS, DU, real>(chi, y, u, wget, cs);                                                          \
+        J += critic_with<DY, DU, real>(chi, y, u, wget, cs);                                                          \
     } else if (SUMF) {                                                                                                \
-      critic_phi_accum<DS, DU, real>(chi, y, u, Phi, CS_C);                                                           \
+      critic_phi_accum<DY, DU, real>(chi, y, u, Phi, CS_C);                                                           \
     } else {                                                                                                          \
-      J += critic_with<DS, DU, real>(chi, y, u, wget, cs);                                                            \
+      J += critic_with<DY, DU, real>(chi, y, u, wget, cs);                                                            \
     }                                                                                                                 \
     if (!G1) gk *= P.gamma;                                                                                           \
 _Pragma("unroll")                                                                                                        \
@@ -471,7 +548,7 @@ _Pragma("unroll")                                                               
     // candidate here as it does in the streamed kernels.  (The skipped inputs are the grid's own bounded levels.)
 #ifndef RCG_AB_NO_ZWP
 #pragma unroll
-    for (int i = 0; i < DS; ++i)
+    for (int i = 0; i < DY; ++i)
       if ((ZW >> i) & 1u) J = fma_r(P.R1d[i], y[i] * y[i], J);
     J += zw0;  // (exactly 0, or NaN: J is unchanged bit for bit whenever every zero-weighted component is finite)
 #endif
@@ -569,22 +646,31 @@ template <typename Sys, typename real, bool TGT, bool G1, int NC, unsigned ZW = 
 __device__ __forceinline__ void rollout_mpc_gen_multi(const KParams<real>& P, const typename Sys::template Pre<real>& pre,
                                                       int N, const real* xs, const real* y0, const real* u0v, real u1,
                                                       real* Jout) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
+  // (with an output map the observation's components are not the state's: only the states are shared)
   constexpr unsigned SH = Sys::SHARED_U1;
+  constexpr unsigned SHY = HasOut<Sys>::value ? 0u : SH;
   static_assert(DU == 2, "candidates of a lane share their second input");
   const real h = P.h_pred;
-  real x[NC][DS], y[NC][DS], u[NC][DU], J[NC], S[NC][G1 ? NCHI : 1];
+  real x[NC][DS], y[NC][DY], u[NC][DU], J[NC], S[NC][G1 ? NCHI : 1];
   real gk = 1;
   real zw0 = 0;  // as rollout_cost
 #pragma unroll
-  for (int i = 0; i < DS; ++i)
+  for (int i = 0; i < DY; ++i)
     if (G1 && ((ZW >> i) & 1u)) zw0 = fma_r(P.R1d[i], y0[i] * y0[i], zw0);
 #pragma unroll
   for (int c = 0; c < NC; ++c) {
+    if constexpr (HasOut<Sys>::value) {
 #pragma unroll
-    for (int i = 0; i < DS; ++i) {
-      x[c][i] = xs[i];
-      y[c][i] = y0[i];
+      for (int i = 0; i < DS; ++i) x[c][i] = xs[i];
+#pragma unroll
+      for (int i = 0; i < DY; ++i) y[c][i] = y0[i];
+    } else {  // (no output map: the statements in their earlier order)
+#pragma unroll
+      for (int i = 0; i < DS; ++i) {
+        x[c][i] = xs[i];
+        y[c][i] = y0[i];
+      }
     }
     u[c][0] = u0v[c];
     u[c][1] = u1;
@@ -601,22 +687,31 @@ __device__ __forceinline__ void rollout_mpc_gen_multi(const KParams<real>& P, co
 #pragma unroll
         for (int i = 0; i < DS; ++i) {
           x[c][i] = fma_r(h, d[i], x[c][i]);
-          y[c][i] = x[c][i];  // sys_out is the identity
+          if constexpr (!HasOut<Sys>::value) y[c][i] = x[c][i];  // no output map: y = x
         }
+        if constexpr (HasOut<Sys>::value) sys_out<Sys, real, true>(pre, x[c], y[c]);
       }
+      if constexpr (HasOut<Sys>::value) {
 #pragma unroll
-      for (int c = 1; c < NC; ++c)
+        for (int c = 1; c < NC; ++c)
 #pragma unroll
-        for (int i = 0; i < DS; ++i)
-          if ((SH >> i) & 1u) {  // identical by construction: name them identically
-            x[c][i] = x[0][i];
-            y[c][i] = y[0][i];
-          }
+          for (int i = 0; i < DS; ++i)
+            if ((SH >> i) & 1u) x[c][i] = x[0][i];  // identical by construction: name them identically
+      } else {
+#pragma unroll
+        for (int c = 1; c < NC; ++c)
+#pragma unroll
+          for (int i = 0; i < DS; ++i)
+            if ((SH >> i) & 1u) {  // identical by construction: name them identically
+              x[c][i] = x[0][i];
+              y[c][i] = y[0][i];
+            }
+      }
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       real chi[NCHI];
-      make_chi<DS, DU, TGT, real>(P, y[c], u[c], chi);
+      make_chi<DY, DU, TGT, real>(P, y[c], u[c], chi);
       if (G1) {
 #pragma unroll
         for (int i = 0; i < NCHI; ++i)
@@ -629,9 +724,9 @@ __device__ __forceinline__ void rollout_mpc_gen_multi(const KParams<real>& P, co
 #pragma unroll
       for (int c = 1; c < NC; ++c) {
 #pragma unroll
-        for (int i = 0; i < DS; ++i)
-          if ((SH >> i) & 1u) S[c][G1 ? i : 0] = S[0][G1 ? i : 0];
-        S[c][G1 ? DS + 1 : 0] = S[0][G1 ? DS + 1 : 0];  // the shared input's own term
+        for (int i = 0; i < DY; ++i)
+          if ((SHY >> i) & 1u) S[c][G1 ? i : 0] = S[0][G1 ? i : 0];
+        S[c][G1 ? DY + 1 : 0] = S[0][G1 ? DY + 1 : 0];  // the shared input's own term
       }
     } else {
       gk *= P.gamma;
@@ -645,7 +740,7 @@ __device__ __forceinline__ void rollout_mpc_gen_multi(const KParams<real>& P, co
         if (!((ZW >> i) & 1u)) J[c] = fma_r(P.R1d[i], S[c][G1 ? i : 0], J[c]);
 #ifndef RCG_AB_NO_ZWP
 #pragma unroll
-      for (int i = 0; i < DS; ++i)  // zero-weighted state components: 0 * inf = NaN, as rollout_cost
+      for (int i = 0; i < DY; ++i)  // zero-weighted observation components: 0 * inf = NaN, as rollout_cost
         if ((ZW >> i) & 1u) J[c] = fma_r(P.R1d[i], y[c][i] * y[c][i], J[c]);
       J[c] += zw0;
 #endif
@@ -881,9 +976,9 @@ __device__ __forceinline__ double opaque_r(double v) {
 }
 template <typename Sys, bool TGT, typename real>
 __device__ __forceinline__ real accum_update(const KParams<real>& P, const real* obs, const real* act, real accum) {
-  constexpr int NCHI = Sys::DS + Sys::DU;
+  constexpr int DY = sys_dy<Sys>(), NCHI = DY + Sys::DU;
   real chi[NCHI];
-  make_chi<Sys::DS, Sys::DU, TGT, real>(P, obs, act, chi);
+  make_chi<DY, Sys::DU, TGT, real>(P, obs, act, chi);
   const real inc = opaque_r(stage_any<NCHI, real>(P, chi) * P.sampling_time);
   return accum + inc;
 }
@@ -899,7 +994,7 @@ template <typename Sys, typename real, bool GENERIC, bool TGT, bool STREAM, bool
 __device__ __forceinline__ void actor_wave(const ActorArgs<real>& A, const KParams<real>& P, const long wave, real* const lds,
                                            const bool staged = false) {
   static_assert(!DIRECT || (STREAM && GENERIC && !PKONLY), "DIRECT is a variant of the streamed generic instance");
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
   const int lane = threadIdx.x & 63;
   const long B = P.B;
   const int K = A.K, N = P.n_actor, R = N * DU;
@@ -914,13 +1009,20 @@ __device__ __forceinline__ void actor_wave(const ActorArgs<real>& A, const KPara
   const long b = env_ok ? b_raw : B - 1;
 
   // per-env inputs (broadcast loads: the lanes of one segment read the same address)
-  real y0[DS], xs[DS];
+  real y0[DY], xs[DS], on[sys_dxy<Sys>()];
+  if constexpr (HasOut<Sys>::value) {  // y_0 from the observation, or out(state) (obs_x)
+    load_obs_raw<Sys, real>(A.obs, A.obs_x, B, b, on);
 #pragma unroll
-  for (int c = 0; c < DS; ++c) {
-    y0[c] = A.obs[(long)c * B + b];
-    xs[c] = A.state_sys[(long)c * B + b];
+    for (int c = 0; c < DS; ++c) xs[c] = A.state_sys[(long)c * B + b];
+  } else {
+#pragma unroll
+    for (int c = 0; c < DS; ++c) {
+      y0[c] = A.obs[(long)c * B + b];
+      xs[c] = A.state_sys[(long)c * B + b];
+    }
   }
   const auto pre = load_pre<Sys, real>(P, A.pars_env, b);
+  if constexpr (HasOut<Sys>::value) obs_of_raw<Sys, real>(pre, A.obs_x, on, y0);
   // critic weights of this lane's env, once, into registers (they were re-read from memory at every use inside the
   // horizon loop: the J store below may alias them, so the compiler cannot hoist the loads itself)
   constexpr int DCMAX = GENERIC ? NCHI * (NCHI + 1) / 2 + NCHI : 1;
@@ -1050,7 +1152,7 @@ template <typename Sys, typename real, bool TGT>
 __device__ __forceinline__ bool env_substeps(const KParams<real>& P, const typename Sys::template Pre<real>& pre,
                                              int n_sub, real* x, real* xp, const real* a_held, uint32_t& st,
                                              real& accum) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = sys_dy<Sys>() + DU;
   if (st & 1u) return false;  // frozen env
   real u[DU], xn[DS], xq[DS];
 #pragma unroll
@@ -1063,8 +1165,9 @@ __device__ __forceinline__ bool env_substeps(const KParams<real>& P, const typen
     for (int c = 0; c < DS; ++c) xq[c] = xn[c];
     rk4_step<Sys, real>(pre, xn, u, P.dt_sim);
     if (P.accum_every_substep) {
-      real chi[NCHI];
-      make_chi<DS, DU, TGT, real>(P, xn, u, chi);
+      real chi[NCHI], yn[sys_dy<Sys>()];
+      sys_out<Sys, real, false>(pre, xn, yn);
+      make_chi<sys_dy<Sys>(), DU, TGT, real>(P, yn, u, chi);
       acc = fma_r(stage_any<NCHI, real>(P, chi), P.sampling_time, acc);
     }
   }
@@ -1212,19 +1315,35 @@ __global__ void k_rhs(const real* state, const real* action, real* dstate, real*
 
 template <typename Sys, typename real>
 __global__ void k_stage_obj(const real* obs, const real* act, real* out, long n, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  real y[DS], u[DU], chi[NCHI];
+  real y[DY], u[DU], chi[NCHI];
 #pragma unroll
-  for (int c = 0; c < DS; ++c) y[c] = obs[(long)c * n + i];
+  for (int c = 0; c < DY; ++c) y[c] = obs[(long)c * n + i];
 #pragma unroll
   for (int c = 0; c < DU; ++c) u[c] = act[(long)c * n + i];
   if (P.has_target)
-    make_chi<DS, DU, true, real>(P, y, u, chi);
+    make_chi<DY, DU, true, real>(P, y, u, chi);
   else
-    make_chi<DS, DU, false, real>(P, y, u, chi);
+    make_chi<DY, DU, false, real>(P, y, u, chi);
   out[i] = stage_any<NCHI, real>(P, chi);
+}
+
+// y = out(x) for n points, lane == point (rcg_out; the Simulator's observation, systems.py:185): the per-env parameters when the
+// caller hands the handle's batch, else the handle's own
+template <typename Sys, typename real>
+__global__ void k_out(const real* state, real* obs, const real* pars_env, long n, const KParams<real> P) {
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>();
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  real x[DS], y[DY];
+#pragma unroll
+  for (int c = 0; c < DS; ++c) x[c] = state[(long)c * n + i];
+  const auto pre = load_pre<Sys, real>(P, pars_env, i);
+  sys_out<Sys, real, false>(pre, x, y);
+#pragma unroll
+  for (int c = 0; c < DY; ++c) obs[(long)c * n + i] = y[c];
 }
 
 template <typename Sys, typename real>

@@ -6,7 +6,8 @@
 // instances through hipModuleLaunchKernel:
 //   at registration  a small probe program (the policy's optional members), then the f32 and f64 core programs: k_rhs,
 //                    k_stage_obj, k_sim, k_actor (streamed / generated x generic / diagonal stage cost x target, and the DIRECT
-//                    long-row form), k_actor_opt without LOOP when the policy has jac_T;
+//                    long-row form), k_actor_opt without LOOP when the policy has jac_T (and out_jac_T if it has out), k_out
+//                    when the policy has an output map `out` (DY = dim_output; every kernel then observes y = out(x));
 //   on first use     k_actor_dma / k_actor_dma_packed at the handle's row length and variant: one small program each, cached;
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan (rcg_sysops.hpp), the functions
@@ -71,12 +72,14 @@ bool is_identifier(const char* s) {
 // The generated unit: the kernel headers, the policy (its own file name and line numbers in hipRTC's log), the adapter that
 // supplies the optional members and the checks of the declared dimensions.
 std::string unit_source(const RtcSystem& S) {
-  char dims[1024];
+  char dims[1536];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
            "static_assert(RcgRtcSys::DU == %d, \"rcg_register_system: %s::DU differs from the declared du\");\n"
-           "static_assert(RcgRtcSys::NP == %d, \"rcg_register_system: %s::NP differs from the declared np\");\n",
-           S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str());
+           "static_assert(RcgRtcSys::NP == %d, \"rcg_register_system: %s::NP differs from the declared np\");\n"
+           "static_assert(RcgRtcSys::HAS_OUT || RcgRtcSys::DY == RcgRtcSys::DS, \"rcg_register_system: %s::DY differs from DS "
+           "but %s defines no out (without an output map the observation is the state)\");\n",
+           S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str());
   const std::string& N = S.name;
   return "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
@@ -91,12 +94,20 @@ std::string unit_source(const RtcSystem& S) {
          "template <class S> struct su1<S, void_t<decltype(S::SHARED_U1)>> { static constexpr unsigned v = S::SHARED_U1; };\n"
          "template <class S, class = void> struct jac { static constexpr bool v = false; };\n"
          "template <class S> struct jac<S, void_t<decltype(&S::template jac_T<float, true>)>> { static constexpr bool v = true; };\n"
-         "template <bool TGT, bool JAC> __global__ void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct out { static constexpr bool v = false; };\n"
+         "template <class S> struct out<S, void_t<decltype(&S::template out<float, true>)>> { static constexpr bool v = true; };\n"
+         "template <class S, class = void> struct ojac { static constexpr bool v = false; };\n"
+         "template <class S> struct ojac<S, void_t<decltype(&S::template out_jac_T<float, true>)>> { static constexpr bool v = true; };\n"
+         "template <class S, class = void> struct dy { static constexpr int v = S::DS; };\n"
+         "template <class S> struct dy<S, void_t<decltype(S::DY)>> { static constexpr int v = S::DY; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
          "  static constexpr unsigned ZW_PRESET = rtc::zw<" + N + ">::v;\n"
          "  static constexpr unsigned SHARED_U1 = rtc::su1<" + N + ">::v;\n"
+         "  static constexpr bool HAS_OUT = rtc::out<" + N + ">::v;\n"
+         "  static constexpr int DY = rtc::dy<" + N + ">::v;\n"
          "};\n" +
          dims + "}  // namespace rcg\n";
 }
@@ -159,6 +170,10 @@ std::string expr_stage_obj() {
   return std::string("rcg::k_stage_obj<") + kSysExpr + ", " + real_name<real>() + ">";
 }
 template <typename real>
+std::string expr_out() {
+  return std::string("rcg::k_out<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+template <typename real>
 std::string expr_sim(bool tgt) {
   return std::string("rcg::k_sim<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ">";
 }
@@ -181,8 +196,10 @@ std::string expr_dma(bool packed, int R, int variant, bool sys_tgt) {
 }
 
 template <typename real>
-std::vector<std::string> core_exprs(bool has_jac) {
+std::vector<std::string> core_exprs(const RtcDims& d) {
+  const bool has_jac = d.has_jac && (!d.has_out || d.has_out_jac);  // (the optimiser's adjoint needs both with an output map)
   std::vector<std::string> e{expr_rhs<real>(), expr_stage_obj<real>(), expr_sim<real>(false), expr_sim<real>(true)};
+  if (d.has_out) e.push_back(expr_out<real>());
   for (int g = 0; g < 2; ++g)
     for (int t = 0; t < 2; ++t) {
       for (int s = 0; s < 2; ++s) e.push_back(expr_actor<real>(g, t, s, false));
@@ -405,6 +422,10 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
   if (!h->rtc->dims.has_jac)
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_actor_optimize: the policy %s defines no jac_T (the optimiser's adjoint sweep)",
                     h->rtc->name.c_str());
+  if (h->rtc->dims.has_out && !h->rtc->dims.has_out_jac)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                    "rcg_actor_optimize: the policy %s defines out but no out_jac_T (the adjoint of its output map)",
+                    h->rtc->name.c_str());
   if (h->loop_io.on) return refuse(h, "rcg_loop_step");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
@@ -455,20 +476,38 @@ int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, i
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC> mangles its arguments as Lb0E / Lb1E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC> mangles its arguments as Lb0E / Lb1E and Li<n>E / Lin<n>E)
 int probe(RtcSystem& S, std::string* log) {
-  const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<rcg::" + S.name + ">::v>";
+  const std::string pol = "rcg::" + S.name;
+  const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
+                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  const size_t a = low.find("Lb"), b = a == std::string::npos ? a : low.find("Lb", a + 3);
-  if (b == std::string::npos) {
+  long v[5];
+  size_t p = low.find("IL");
+  int n = 0;
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 5 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+    const char t = low[p + 1];
+    size_t q = p + 2;
+    const bool neg = t == 'i' && low[q] == 'n';
+    if (neg) ++q;
+    long x = 0;
+    while (q < low.size() && isdigit((unsigned char)low[q])) x = 10 * x + (low[q++] - '0');
+    if ((t != 'b' && t != 'i') || q >= low.size() || low[q] != 'E') break;
+    v[n] = neg ? -x : x;
+    p = q + 1;
+  }
+  if (n != 5) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
-  S.tgt = low[a + 2] == '1';
-  S.dims.has_jac = low[b + 2] == '1';
+  S.tgt = v[0] != 0;
+  S.dims.has_jac = v[1] != 0;
+  S.dims.dy = (int)v[2];
+  S.dims.has_out = v[3] != 0;
+  S.dims.has_out_jac = S.dims.has_out && v[4] != 0;
   return RCG_OK;
 }
 
@@ -479,6 +518,22 @@ const SysVTable kVtRtc = {&rtc_rhs,     &rtc_stage_obj, &rtc_critic,   &rtc_crit
                           &rtc_sim_step, &rtc_critic_update, &rtc_optimize, &rtc_nominal, &rtc_ticks,
                           &rtc_rhs_full, &rtc_search,    &rtc_ticks,    &rtc_loop};
 #endif
+
+int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = core_function<real>(h, expr_out<real>(), &f);
+    if (rc) return rc;
+    const real* st = (const real*)state;
+    real* y = (real*)obs;
+    const real* pe = (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
+    long nn = n;
+    KParams<real> P = params<real>(h);
+    void* args[] = {&st, &y, &pe, &nn, &P};
+    return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+  });
+}
 
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims) {
   std::lock_guard<std::mutex> lock(g_mu);
@@ -522,12 +577,16 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   std::unique_ptr<RtcSystem> S(new RtcSystem);
   S->name = name;
   S->src = policy_src;
-  S->dims = RtcDims{ds, du, np, false};
+  S->dims = RtcDims{ds, du, np, false, ds, false, false};
   S->tgt = false;
   std::string log;
   rc = probe(*S, &log);
-  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f32.hip", core_exprs<float>(S->dims.has_jac), &S->core[0], &log);
-  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f64.hip", core_exprs<double>(S->dims.has_jac), &S->core[1], &log);
+  // dim_output: chi = [y - target, u] must fit RCG_MAX_CHI and the target KParams::target (a DY other than DS without `out` is
+  // refused by the adapter's static_assert above, with hipRTC's log)
+  if (rc == RCG_OK && (S->dims.dy < 1 || S->dims.dy > RCG_MAX_DS))
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::DY = %d beyond 1 .. %d", name, S->dims.dy, RCG_MAX_DS);
+  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f32.hip", core_exprs<float>(S->dims), &S->core[0], &log);
+  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f64.hip", core_exprs<double>(S->dims), &S->core[1], &log);
   if (rc) {
     rcg_set_thread_error(std::string("rcg_register_system: ") + name + ": " + log);
     return rc;

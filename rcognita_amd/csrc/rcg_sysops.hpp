@@ -418,6 +418,11 @@ static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_t
     A.state_sys = (const real*)obs;
   else
     A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  // without an observation the kernel is handed the handle's STATE and observes y_0 = out(STATE) (identity for the built-ins);
+  // an observation [dy][B] is not a state when dy != ds, so it needs state_sys
+  A.obs_x = obs ? 0 : 1;
+  if (obs && !state_sys && h->dy != h->ds)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: an observation of dim_output %d != dim_state %d needs state_sys", who, h->dy, h->ds);
   A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
   A.w = w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC];
   if (c.mode != RCG_MODE_MPC && !A.w)
@@ -777,6 +782,10 @@ static int opt_plan(rcg_handle* h, int du, int32_t iters, const void* obs, const
     A.state_sys = (const real*)obs;
   else
     A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  A.obs_x = obs ? 0 : 1;  // as actor_plan
+  if (obs && !state_sys && h->dy != h->ds)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_optimize: an observation of dim_output %d != dim_state %d needs state_sys", h->dy,
+                    h->ds);
   A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
   A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
   if (c.mode != RCG_MODE_MPC && !A.w)

@@ -56,7 +56,8 @@ class EngineConfig:
 
     def to_native(self) -> N.RcgCfg:
         ds, du, npar = N.SYS_DIMS[self.sys_id]
-        n = ds + du
+        dy = N.sys_dy(self.sys_id)  # dim_output: chi = [y - target, u]
+        n = dy + du
         c = N.RcgCfg()
         c.struct_size = C.sizeof(N.RcgCfg)
         c.sys_id, c.batch, c.device = int(self.sys_id), int(self.batch), int(self.device)
@@ -92,15 +93,15 @@ class EngineConfig:
                 for j in range(n):
                     arr[i * n + j] = M[i, j]
         if self.observation_target is not None and len(self.observation_target) > 0:
-            t = np.asarray(self.observation_target, dtype=np.float64).reshape(ds)
-            for i in range(ds):
+            t = np.asarray(self.observation_target, dtype=np.float64).reshape(dy)
+            for i in range(dy):
                 c.target[i] = t[i]
             flags |= N.FLAG_HAS_TARGET
         a0 = bnds[:, 0] / 10.0 if self.action_init is None or len(self.action_init) == 0 else np.asarray(
             self.action_init, dtype=np.float64).reshape(du)
         for i in range(du):
             c.action_init[i] = a0[i]
-        dc = dim_critic(self.critic_struct, ds, du)
+        dc = dim_critic(self.critic_struct, dy, du)  # (rcg_create: the critic's regressor is over [y, u])
         lo, hi = critic_bounds(self.critic_struct)
         for i in range(dc):
             c.w_init[i], c.w_min[i], c.w_max[i] = 1.0, lo, hi  # controllers.py:1026-1042
@@ -243,7 +244,7 @@ class Engine:
         L = N.lib()
         self.ds, self.du, self.npar = N.SYS_DIMS[cfg.sys_id]
         self.dd = N.DIM_DISTURB.get(int(cfg.sys_id), 0)  # (a system registered at run time has no disturbance model)
-        self.dy = self.ds
+        self.dy = N.sys_dy(cfg.sys_id)  # dim_output (a registered system's DY; the state's dimension otherwise)
         self.B = int(cfg.batch)
         self.N = int(cfg.Nactor)
         self.real = np.float32 if cfg.dtype == "f32" else np.float64
@@ -515,6 +516,17 @@ class Engine:
         bits, xi = self._tmp((4, self.B), np.uint32), self._tmp((2, self.B))
         N.check(N.lib().rcg_disturb_noise(self._h, C.c_void_p(bits.ptr), C.c_void_p(xi.ptr)), self._h)
         return bits.to_host().T.copy(), xi.to_host().T.copy()
+
+    def out(self, state):
+        """``System.out`` (systems.py:185) on ``n`` points: ``state [n, ds]`` -> ``obs [n, dy]`` (rcg_out; without an output map
+        the observation is the state)."""
+        state = np.asarray(state, dtype=self.real).reshape(-1, self.ds)
+        n = state.shape[0]
+        keep = []
+        ps = self._in(state, keep, lambda a: a.T)
+        y = self._tmp((self.dy, n))
+        N.check(N.lib().rcg_out(self._h, ps, C.c_void_p(y.ptr), n), self._h)
+        return y.to_host().T.copy()
 
     def stage_obj(self, obs, act):
         obs = np.asarray(obs, dtype=self.real).reshape(-1, self.dy)

@@ -41,7 +41,8 @@ class System:
             if is_disturb:
                 raise NotImplementedError("a system compiled from hip_policy has no disturbance model (is_disturb=1)")
             if type(self).out is not System.out:
-                raise NotImplementedError("a system compiled from hip_policy has output = state: `out` cannot be overridden")
+                raise NotImplementedError("a system compiled from hip_policy cannot override `out` in Python (there is no CPU "
+                                          "path): give the policy an `out` member (and DY, out_jac_T; INTEGRATION.md)")
             self._register_hip_policy(dim_state, dim_input, pars)
         if self._sys_id is None:
             raise NotImplementedError(
@@ -52,10 +53,11 @@ class System:
         if is_dyn_ctrl:
             raise NotImplementedError("is_dyn_ctrl is out of scope (SURVEY.md 8a row 1)")
         ds, du, npar = N.SYS_DIMS[self._sys_id]
+        dy = N.sys_dy(self._sys_id)  # a hip_policy's DY (its output map), else the state's dimension
         if is_disturb and dim_disturb != N.DIM_DISTURB[self._sys_id]:
             raise ValueError(f"{type(self).__name__} has dim_disturb = {N.DIM_DISTURB[self._sys_id]}")
-        if (dim_state, dim_input, dim_output) != (ds, du, ds):
-            raise ValueError(f"{type(self).__name__} has dims (state, input, output) = ({ds}, {du}, {ds})")
+        if (dim_state, dim_input, dim_output) != (ds, du, dy):
+            raise ValueError(f"{type(self).__name__} has dims (state, input, output) = ({ds}, {du}, {dy})")
         self.sys_type = sys_type
         self.dim_state, self.dim_input, self.dim_output, self.dim_disturb = dim_state, dim_input, dim_output, dim_disturb
         self.pars = pars
@@ -177,8 +179,14 @@ class System:
         return np.zeros(self.dim_input)
 
     def out(self, state, action=[]):
-        """System output = state for all built-in systems (rcognita/systems.py:185-198)."""
-        return state
+        """System output (rcognita/systems.py:185-198): the state for the built-in systems; for a ``hip_policy`` with an
+        ``out`` member, y = out(state) computed on the device (rcg_out), ``[dy]`` or ``[B, dy]``."""
+        info = type(self)._hip_info
+        if info is None or not info.get("has_out"):
+            return state
+        x = np.asarray(state, dtype=float)
+        y = self._engine().out(x.reshape(-1, self.dim_state))
+        return y.reshape(x.shape[:-1] + (self.dim_output,)).astype(float)
 
     def receive_action(self, action):
         """rcognita/systems.py:200-211."""

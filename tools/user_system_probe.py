@@ -5,7 +5,9 @@ Registers the pendulum of INTEGRATION.md (DS 2, DU 1, NP 3; wall time of the cal
 one handle per element type and times the first streamed decision (it compiles k_actor_dma at the handle's row length), then
 times the streamed f64 tick at 65 536 envs x 256 candidates x Nactor 10 from the dispatches' own stamps (rcg_profile) on the
 pendulum, on the small-angle pendulum (no trigonometry) and on Sys2Tank (same DS / DU, same kernel shape), as a fraction of
-8 TB/s of candidate bytes.  GPU box only; no torch.
+8 TB/s of candidate bytes.  The same for the pendulum with an output map y = (sin th, cos th, om) (DY = 3, out, out_jac_T;
+DESIGN.md §13.1): its registration, its first streamed tick and its streamed f64 tick next to the pendulum without one.
+GPU box only; no torch.
 
     python tools/user_system_probe.py [B] [K] [Nactor]
 """
@@ -53,6 +55,27 @@ struct PendulumT {
 # the same shape without trigonometry (the small-angle pendulum, sin x ~ x): separates the cost of the f64 sine in the rollout
 # from everything else the runtime path does
 PENDULUM_LIN = PENDULUM.replace("sincos_sel<real, HW>(x[0], &s, &c);", "s = x[0];\n    c = (real)1;")
+# with an output map: y = (sin th, cos th, om), the cost on (sin th, cos th) instead of th^2
+PENDULUM_OUT = PENDULUM.replace("static constexpr int DS = 2, DU = 1, NP = 3;",
+                                "static constexpr int DS = 2, DU = 1, NP = 3;\n  static constexpr int DY = 3;").replace("\n};\n", r'''
+  template <typename real, bool HW = false>
+  __device__ __forceinline__ static void out(const Pre<real>&, const real* x, real* y) {
+    real s, c;
+    sincos_sel<real, HW>(x[0], &s, &c);
+    y[0] = s;
+    y[1] = c;
+    y[2] = x[1];
+  }
+  template <typename real, bool HW = false>
+  __device__ __forceinline__ static void out_jac_T(const Pre<real>&, const real* x, const real* gy, real* gx) {
+    real s, c;
+    sincos_sel<real, HW>(x[0], &s, &c);
+    gx[0] = c * gy[0] - s * gy[1];
+    gx[1] = gy[2];
+  }
+};
+''')
+R1_OUT = np.diag([5.0, 5.0, 0.5, 0.1])
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
@@ -62,29 +85,35 @@ PEAK = 8e12
 info = N.register_system("PendulumProbe", PENDULUM.replace("PendulumT", "PendulumProbe"), 2, 1, 3)
 print(f"hiprtc {info['hiprtc']}: rcg_register_system {info['seconds']:.2f} s (probe + f32 + f64 core programs)")
 lin = N.register_system("PendulumLinProbe", PENDULUM_LIN.replace("PendulumT", "PendulumLinProbe"), 2, 1, 3)
+out = N.register_system("PendulumOutProbe", PENDULUM_OUT.replace("PendulumT", "PendulumOutProbe"), 2, 1, 3)
+print(f"with out (DY {out['dy']}): rcg_register_system {out['seconds']:.2f} s (probe + f32 + f64 core programs, k_out)")
 
 
-def engine(sid, dtype, pars):
+def engine(sid, dtype, pars, R1=None):
     return Engine(EngineConfig(sys_id=sid, batch=B, dtype=dtype, Nactor=NH, pars=pars, ctrl_bnds=np.array([[-5.0, 5.0]]),
-                               R1=np.diag([10.0, 1.0, 0.1]), dt_sim=0.01, sampling_time=0.01, pred_step_size=0.02))
+                               R1=np.diag([10.0, 1.0, 0.1]) if R1 is None else R1, dt_sim=0.01, sampling_time=0.01,
+                               pred_step_size=0.02))
 
 
 rng = np.random.default_rng(0)
-for dtype in ("f32", "f64"):
-    e = engine(info["sys_id"], dtype, [1.3, 9.81, 0.7])
-    e.set_state(rng.uniform(-1, 1, (B, 2)))
-    cand = e.to_device(rng.uniform(-5, 5, (B, K, NH, 1)))
-    t0 = time.perf_counter()
-    e.control_tick(cand)
-    e.synchronize()
-    print(f"{dtype}: first streamed tick (compiles {e.last_launch()['kernel']} at R = {NH}) {time.perf_counter() - t0:.2f} s")
-    e.close()
+for label, sid, R1 in (("", info["sys_id"], None), ("with out, ", out["sys_id"], R1_OUT)):
+    for dtype in ("f32", "f64"):
+        e = engine(sid, dtype, [1.3, 9.81, 0.7], R1)
+        e.set_state(rng.uniform(-1, 1, (B, 2)))
+        cand = e.to_device(rng.uniform(-5, 5, (B, K, NH, 1)))
+        t0 = time.perf_counter()
+        e.control_tick(cand)
+        e.synchronize()
+        print(f"{label}{dtype}: first streamed tick (compiles {e.last_launch()['kernel']} at R = {NH}) "
+              f"{time.perf_counter() - t0:.2f} s")
+        e.close()
 
 rows = []
-for name, sid, pars in (("pendulum (runtime)", info["sys_id"], [1.3, 9.81, 0.7]),
-                        ("small-angle (runtime)", lin["sys_id"], [1.3, 9.81, 0.7]),
-                        ("Sys2Tank (built-in)", N.SYS_2TANK, [15.0, 15.0, 1.0, 1.0, 0.1])):
-    e = engine(sid, "f64", pars)
+for name, sid, pars, R1 in (("pendulum (runtime)", info["sys_id"], [1.3, 9.81, 0.7], None),
+                            ("pendulum with out", out["sys_id"], [1.3, 9.81, 0.7], R1_OUT),
+                            ("small-angle (runtime)", lin["sys_id"], [1.3, 9.81, 0.7], None),
+                            ("Sys2Tank (built-in)", N.SYS_2TANK, [15.0, 15.0, 1.0, 1.0, 0.1], None)):
+    e = engine(sid, "f64", pars, R1)
     e.set_state(rng.uniform(0, 1, (B, 2)))
     cand = e.to_device(rng.uniform(-5, 5, (B, K, NH, 1)))
     for _ in range(5):
