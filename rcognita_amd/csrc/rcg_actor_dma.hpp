@@ -12,14 +12,30 @@
 //   per tile of 64 candidate rows (64*R*sizeof(real) bytes, contiguous in HBM):
 //     1. direct-to-LDS loads: global_load_lds_dwordx4 (64 lanes x 16 B = 1 KiB each) plus global_load_lds_dword (256 B
 //        each) for the remainder, `nt` (the tensor is read once per tick) - fully coalesced, written by the memory
-//        pipeline straight into this wave's LDS tile, no VGPR staging;
+//        pipeline straight into this wave's LDS tile, no VGPR staging.  A full tile is addressed as scalar base (the
+//        tile's, wave-uniform, in SGPRs) + the lane's 32-bit offset + an immediate: between a tile's landing and the last
+//        re-issued load there is no 64-bit vector address arithmetic (two 32-bit adds for ten pieces).  A ragged tile
+//        masks its pieces per lane in a branch of its own, which the full-tile path does not pay for;
 //     2. the lane pulls ITS row LDS -> registers (R reals at lane*R*sizeof(real): ds_read_b128 / b64 / b32 as the
 //        alignment allows; R = 20 floats is conflict-free, any residual conflict is noise next to the rollout);
 //     3. as soon as the row is in registers the SAME LDS tile is free again: the next tile's loads are issued
-//        here, before the rollout, so they are in flight during all of step 4;
+//        here, before the rollout, so they are in flight during all of step 4.  A wave has one tile, so landing ->
+//        re-issue is the one stretch in which it has nothing in flight: whatever can wait runs behind it.  Adopting an
+//        env (every T tiles: register moves, the state-lag selects, parking the critic weights, the shared rollout
+//        prefix) does; the values derived from the parameters (1/m ...: float64 divisions) are computed once per launch
+//        unless the handle has per-env parameters - then per env, in front of the landing wait (behind the re-issue
+//        their temporaries are live together with the lane's row: +10 VGPRs, a wave per SIMD on the tank);
 //     4. the rollout runs on registers only, the horizon fully unrolled (N = R/du is a template constant): no
 //        wait of any kind.  Trig: f32 hardware v_sin/v_cos behind an exact reduction (rcg_math.hpp::sincos_hw); f64 a
 //        Cody-Waite reduction + minimax polynomials (sincos_fast, ~40 VALU ops against libm's several hundred).
+//        Shared prefix (policies with the hook of rcg_systems.hpp - the 3-wheel robot; no output map): the components of
+//        x_1 that the action does not enter (x, y, alpha), sincos(alpha_0), sincos(alpha_1) and, for DMA_MPC_G1, the
+//        cost terms of y_0 and of those components of y_1 are the same for the K candidates of an env.  The wave computes
+//        them once when it adopts the env - the policy's own rhs_trig and the same fma_r calls on the same operands, so
+//        every candidate's cost keeps its bits - and holds them (and the env's state) in SCALAR registers
+//        (v_readfirstlane): 2 of the 9 sincos of a Nactor = 10 rollout and 7 accumulations go, 491 -> 417 instructions
+//        per tile in f64, for ~140 per env (T = 4 tiles), at 161 VGPRs (159 before); measured: DESIGN.md 6.  Horizons of
+//        1 and 2 steps take the part of the prefix they have;
 // The only vmcnt wait is the one in front of step 2 of the NEXT tile, which is exactly the data it needs.
 // vmcnt retires in issue order, so whatever else the next iteration needs from memory (the next env's state)
 // is requested BEFORE the tile loads and never drains them.
@@ -35,8 +51,10 @@
 // bare data path of this kernel (steps 1-3, no arithmetic) holds 7.0-7.2 TB/s (tools/bw_probe.hip residency).  In a
 // development build (`make dev`, -DRCG_DEV -> librcg_dev.so) the A.dbg bits (env RCG_DBG) switch pieces off for such
 // measurements: 1 rollout, 2 argmin + writes, 4 env-state loads.  The production library compiles them out.
-// Tried and removed (DESIGN.md 4): two tiles in flight per wave (1.5-3 % slower), the tick's env step fused into the
+// Tried and removed (DESIGN.md 5): two tiles in flight per wave (1.5-3 % slower), the tick's env step fused into the
 // prologue (a wash: +3-4 % kernel time against one saved 7-us launch).
+// s_setprio around landing -> re-issue (RCG_DMA_PRIO, off): no effect on the f32 kernel in round 2; the float64 A/B of this
+// change is recorded in DESIGN.md 6.  The tank's and the kinematic robot's prefix hooks (registers: rcg_systems.hpp).
 #pragma once
 #include <hip/hip_ext.h>
 #include "rcg_kernels.hpp"
@@ -46,6 +64,11 @@
 // -DRCG_DMA_AUX=...): see DESIGN.md 4.
 #ifndef RCG_DMA_AUX
 #define RCG_DMA_AUX 2
+#endif
+// s_setprio level of a float64 wave between its tile's landing wait and the last re-issued load (0: none).  An A/B knob
+// (`make ab ABFLAGS=-DRCG_DMA_PRIO=1`): see "Tried and removed" above and DESIGN.md 6.
+#ifndef RCG_DMA_PRIO
+#define RCG_DMA_PRIO 0
 #endif
 
 namespace rcg {
@@ -124,6 +147,61 @@ __device__ __forceinline__ void wave_argmin(double& bestJ, int& bestI) {
   }
 }
 
+// A policy with the optional prefix hook (rcg_systems.hpp: PFX_FREE, PFX_HEADING, rhs_trig); one without it compiles to the
+// plain rollout
+template <typename S, typename = void>
+struct HasPrefix {
+  static constexpr bool value = false;
+};
+template <typename S>
+struct HasPrefix<S, void_t_<decltype(S::PFX_FREE)>> {
+  static constexpr bool value = true;
+};
+template <typename S>
+constexpr unsigned pfx_free() {
+  if constexpr (HasPrefix<S>::value)
+    return S::PFX_FREE;
+  else
+    return 0u;
+}
+template <typename S>
+constexpr int pfx_heading() {
+  if constexpr (HasPrefix<S>::value)
+    return S::PFX_HEADING;
+  else
+    return -1;
+}
+
+// a value that is the same in every lane, moved to scalar registers (v_readfirstlane): what an env's candidates share
+// costs no VGPR across the tile loop
+__device__ __forceinline__ float uniform_r(float v) {
+  return __uint_as_float((unsigned)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v)));
+}
+__device__ __forceinline__ double uniform_r(double v) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+  const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)b);
+  const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(b >> 32));
+  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+}
+
+// pieces J .. NP - 1 of a full tile, PIECE bytes per wave-instruction each: the instruction's immediate offset (it counts
+// for the global and for the LDS address alike, and is a compile-time constant of at most 4095) walks four 1-KiB pieces,
+// then the lane's 32-bit offset and the LDS base step on; g is the tile's wave-uniform base
+template <int J, int NP, int SZ, int PIECE>
+__device__ __forceinline__ void dma_pieces(const unsigned char* g, unsigned off, unsigned char* l) {
+  typedef __attribute__((address_space(3))) void lds_void;
+  typedef const __attribute__((address_space(1))) void glb_void;
+  if constexpr (J < NP) {
+    constexpr int BASE = (J * PIECE / 4096) * 4096;
+    const unsigned char* const gb = g + (off + (unsigned)BASE);  // scalar base + one 32-bit vector offset per group
+    if constexpr (SZ == 16)  // (the size must be a literal)
+      __builtin_amdgcn_global_load_lds((glb_void*)gb, (lds_void*)(l + BASE), 16, J * PIECE - BASE, RCG_DMA_AUX);
+    else
+      __builtin_amdgcn_global_load_lds((glb_void*)gb, (lds_void*)(l + BASE), 4, J * PIECE - BASE, RCG_DMA_AUX);
+    dma_pieces<J + 1, NP, SZ, PIECE>(g, off, l);
+  }
+}
+
 // Rows per lane and tile.  A tile is one round trip to HBM per wave whatever its size, so very short rows move few
 // bytes per trip: rows of <= 24 bytes (the robots' Nactor <= 3 in f32) are taken four per lane (tiles of 256 rows), rows
 // of <= 32 bytes two per lane.  One instance per row length: a K that is not a multiple of the tile is a ragged last tile
@@ -148,6 +226,12 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   constexpr int WREG = WLDS ? 1 : DCMAX;             // register copies of the weights (current env, next env)
   static_assert(R % DU == 0 && R >= DU && R <= 40, "row = N*du reals, at most 40 (f32: 160 bytes, f64: 320)");
   constexpr int N = R / DU;
+  // shared rollout prefix (policies with the hook, no output map): what the first steps of an env's rollouts have in common
+  constexpr bool PFX = HasPrefix<Sys>::value && !OUT;
+  constexpr unsigned FREE = PFX ? pfx_free<Sys>() : 0u;  // components of x_1 that do not involve the action
+  constexpr int HD = PFX ? pfx_heading<Sys>() : -1;      // the heading
+  constexpr bool TRIG0 = PFX && HD >= 0 && N >= 2;        // sincos(alpha_0) is shared
+  constexpr bool TRIG1 = TRIG0 && ((FREE >> (HD >= 0 ? HD : 0)) & 1u) && N >= 3;  // so is sincos(alpha_1)
   constexpr int RPL = dma_rpl(R, ESZ), TROWS = 64 * RPL;           // rows per lane, rows per tile
   constexpr int TILE = TROWS * R * ESZ;                            // bytes of one tile
   constexpr int NFULL = TILE / 1024, NREM = (TILE % 1024) / 256;  // 1-KiB and 256-B direct-to-LDS loads per tile
@@ -174,7 +258,16 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 
   unsigned char* const tile = smem_raw + (size_t)wave_in_wg * TILE;  // this wave's LDS tile
   const size_t env_stride = (size_t)K * (R * ESZ);                    // bytes of one env's rows
-  const unsigned char* envb = reinterpret_cast<const unsigned char*>(A.cand) + (size_t)env0 * env_stride;  // env b's rows
+  // env b's rows.  The base is wave-uniform and kept in scalar registers (readfirstlane of its halves: provable to the
+  // compiler); a lane adds the constant 32-bit offset of its piece
+  const unsigned char* envb;
+  {
+    const unsigned long long p = (unsigned long long)(reinterpret_cast<const unsigned char*>(A.cand) + (size_t)env0 * env_stride);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)p);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(p >> 32));
+    envb = reinterpret_cast<const unsigned char*>(((unsigned long long)hi << 32) | lo);
+  }
+  const unsigned lane16 = (unsigned)lane * 16u, lane4 = (unsigned)lane * 4u;
   // operator mode (rcg_actor_cost): the J of one env is staged in LDS ([K] reals per wave, behind the tiles of all
   // four waves) and written out at the env's end in 1-KiB bursts; a 256-B store after every tile, interleaved with
   // the read stream, made the operator 35 % slower than the tick for 5 % more bytes
@@ -187,31 +280,37 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   // `rows` (wave-uniform): TROWS, or rem_rows for an env's ragged last tile - then every lane loads only pieces that lie
   // inside the env's rows (rows * R * ESZ bytes, a multiple of 16), the rest of the LDS tile keeps stale rows that no
   // valid candidate index points at
+  // A full tile: scalar base + the lane's constant offset + an immediate (at most 4095: four 1-KiB pieces per base, the
+  // instruction adds the immediate to the LDS address as well) - no vector address arithmetic between landing and re-issue.
   auto issue_tile = [&](const unsigned char* g, int rows) {
+    // (the lane's 32-bit offsets are re-materialised here, opaquely: widened once outside the loop they come back as 64-bit
+    // register pairs - one per piece - and the loads take a vector address again)
+    // (`rows` likewise: "full tile?" decided here by one scalar compare - as a loop invariant it becomes a 64-bit mask that
+    // is spilled and read back with v_readlane in front of every re-issue; and the ragged branch's per-lane masks, which
+    // derive from it, stay inside that branch instead of being hoisted and carried through the full-tile path)
+    unsigned o16 = lane16, o4 = lane4;
+    if (NFULL) asm volatile("" : "+v"(o16));
+    if (NREM) asm volatile("" : "+v"(o4));
+    asm volatile("" : "+s"(rows));
     if (rows == TROWS) {
-#pragma unroll
-      for (int j = 0; j < NFULL; ++j)
-        __builtin_amdgcn_global_load_lds((glb_void*)(g + j * 1024 + lane * 16), (lds_void*)(tile + j * 1024), 16, 0,
-                                         RCG_DMA_AUX);
-#pragma unroll
-      for (int j = 0; j < NREM; ++j)
-        __builtin_amdgcn_global_load_lds((glb_void*)(g + NFULL * 1024 + j * 256 + lane * 4),
-                                         (lds_void*)(tile + NFULL * 1024 + j * 256), 4, 0, RCG_DMA_AUX);
+      dma_pieces<0, NFULL, 16, 1024>(g, o16, tile);
+      dma_pieces<0, NREM, 4, 256>(g + NFULL * 1024, o4, tile + NFULL * 1024);
     } else {
-      const int vb = rows * (R * ESZ);  // valid bytes of the tile
+      const int vb = rows * (R * ESZ);  // valid bytes of the tile (the compares' right-hand sides are scalar)
 #pragma unroll
       for (int j = 0; j < NFULL; ++j)
-        if (j * 1024 + lane * 16 < vb)
-          __builtin_amdgcn_global_load_lds((glb_void*)(g + j * 1024 + lane * 16), (lds_void*)(tile + j * 1024), 16, 0,
+        if ((int)o16 < vb - j * 1024)
+          __builtin_amdgcn_global_load_lds((glb_void*)(g + (o16 + (unsigned)(j * 1024))), (lds_void*)(tile + j * 1024), 16, 0,
                                            RCG_DMA_AUX);
 #pragma unroll
       for (int j = 0; j < NREM; ++j)
-        if (NFULL * 1024 + j * 256 + lane * 4 < vb)
-          __builtin_amdgcn_global_load_lds((glb_void*)(g + NFULL * 1024 + j * 256 + lane * 4),
+        if ((int)o4 < vb - (NFULL * 1024 + j * 256))
+          __builtin_amdgcn_global_load_lds((glb_void*)(g + (o4 + (unsigned)(NFULL * 1024 + j * 256))),
                                            (lds_void*)(tile + NFULL * 1024 + j * 256), 4, 0, RCG_DMA_AUX);
     }
   };
-  auto rows_of = [&](int tt) -> int { return (tt == T - 1 && rem_rows) ? rem_rows : TROWS; };
+  const int last_rows = rem_rows ? rem_rows : TROWS;  // rows of an env's last tile
+  auto rows_of = [&](int tt) -> int { return tt == T - 1 ? last_rows : TROWS; };
 
   // env state: `n`-suffixed = requested one tile ahead for the next env.  Loads only, no
   // "pointer ? load : default" selects (a default written into a register with a load in flight would force a
@@ -305,7 +404,16 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   const real h = P.h_pred;
   long b = env0;
   int t = 0;
+  // without per-env parameters the derived values (1/m ...: divisions) are the launch's: once, here
+  const bool env_pars = A.pars_env != nullptr;  // wave-uniform
   auto pre_env = Sys::template prepare<real>(pn);
+  // what the candidates of env b share (PFX; wave-uniform, in scalar registers): the action-free components of x_1, the
+  // trig of alpha_1, and the cost terms of y_0 (and of those components of y_1) as the rollout would have summed them
+  real x1s[DS], trig0[2] = {0, 0}, trig1[2] = {0, 0}, Sini[DY];
+#pragma unroll
+  for (int c = 0; c < DS; ++c) x1s[c] = 0;
+#pragma unroll
+  for (int c = 0; c < DY; ++c) Sini[c] = 0;
   real bestJ = inf_r<real>();
   int bestI = 0x7fffffff;
   real bu[DU];
@@ -318,34 +426,94 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 #pragma unroll
   for (int c = 0; c < DU; ++c) resU[c] = 0;
 
-  for (int g = 0; g < n_tiles; ++g) {
-    if (t == 0) {  // first tile of env b: adopt the state requested one tile ago
-      if constexpr (OUT) {
+  // Adopting env b (first tile of the env), in two parts.  adopt_regs: the state requested one tile ago moves into the env's
+  // registers (and its critic weights are parked: the previous env's rollouts are done, program order) - this has to
+  // precede the NEXT env's request, which reuses the `n` registers.  adopt_rest: everything computed from it.  Only
+  // what must sits between a tile's landing and the re-issue of its LDS slot: with more than one tile per env both parts
+  // run behind the re-issue.
+  auto adopt_regs = [&]() {
+    if constexpr (OUT) {
 #pragma unroll
-        for (int c = 0; c < DS; ++c) x0[c] = lag ? xn[c] : yn[c];
-      } else {
-#pragma unroll
-        for (int c = 0; c < DS; ++c) {
-          y0[c] = yn[c];
-          x0[c] = lag ? xn[c] : yn[c];
-        }
-      }
+      for (int c = 0; c < DS; ++c) x0[c] = lag ? xn[c] : yn[c];
 #pragma unroll
       for (int i = 0; i < NP; ++i) pv[i] = pn[i];
       pre_env = Sys::template prepare<real>(pv);
-      if constexpr (OUT) obs_of_raw<Sys, real>(pre_env, A.obs_x, yn, y0);
-      if (CRIT && WLDS) {  // the previous env's rollouts are done (program order): its weights may be overwritten
-        if (lane < dc_rt) wl[lane] = wnl;
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_wave_barrier();
-      } else if (CRIT) {
+      obs_of_raw<Sys, real>(pre_env, A.obs_x, yn, y0);
+    } else {
 #pragma unroll
-        for (int i = 0; i < WREG; ++i) wc[i] = wn[i];
+      for (int c = 0; c < DS; ++c) {
+        y0[c] = yn[c];
+        x0[c] = lag ? xn[c] : yn[c];
       }
-      bestJ = inf_r<real>();
-      bestI = 0x7fffffff;
+    }
+    if (CRIT && WLDS) {
+      if (lane < dc_rt) wl[lane] = wnl;
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_wave_barrier();
+    } else if (CRIT) {
+#pragma unroll
+      for (int i = 0; i < WREG; ++i) wc[i] = wn[i];
+    }
+  };
+  auto adopt_rest = [&]() {
+    if constexpr (PFX) {
+      // the state the rollouts start from is wave-uniform as well: in scalar registers it frees the vector registers that
+      // the shared values would otherwise cost the rollout (f64 headline instance: 10 VGPRs).  y_0 stays where it is: it is
+      // read again only by upd_accum_obj at the env's end, and ten more live SGPRs pushed the tile base into a spill slot
+#pragma unroll
+      for (int c = 0; c < DS; ++c) x0[c] = uniform_r(x0[c]);
+      // the same operations on the same operands as a candidate's own rollout would run (fma_r and the policy's rhs_trig)
+      if constexpr (TRIG0) {
+        sincos_sel<real, true>(x0[HD], &trig0[0], &trig0[1]);
+        if constexpr (FREE != 0) {
+          real uz[DU], d[DS];
+#pragma unroll
+          for (int c = 0; c < DU; ++c) uz[c] = 0;  // (the components taken do not read it)
+          Sys::template rhs_trig<real>(pre_env, x0, uz, trig0[0], trig0[1], d);
+#pragma unroll
+          for (int c = 0; c < DS; ++c)
+            if ((FREE >> c) & 1u) x1s[c] = uniform_r(fma_r(h, d[c], x0[c]));
+        }
+        if constexpr (TRIG1) {
+          sincos_sel<real, true>(x1s[HD], &trig1[0], &trig1[1]);
+          trig1[0] = uniform_r(trig1[0]);
+          trig1[1] = uniform_r(trig1[1]);
+        }
+        if constexpr (FREE == 0) {  // the candidates' first step takes the trig itself
+          trig0[0] = uniform_r(trig0[0]);
+          trig0[1] = uniform_r(trig0[1]);
+        }
+      }
+      if constexpr (G1) {
+#pragma unroll
+        for (int c = 0; c < DY; ++c) {
+          const real chi0 = TGT ? y0[c] - P.target[c] : y0[c];
+          real a = fma_r(chi0, chi0, (real)0);
+          if (N >= 2 && ((FREE >> c) & 1u)) {
+            const real chi1 = TGT ? x1s[c] - P.target[c] : x1s[c];
+            a = fma_r(chi1, chi1, a);
+          }
+          Sini[c] = uniform_r(a);
+        }
+      }
+    }
+    bestJ = inf_r<real>();
+    bestI = 0x7fffffff;
+  };
+  const bool adopt_early = OUT || T == 1;  // one tile per env: the re-issue below already requests the next env's state
+
+  for (int g = 0; g < n_tiles; ++g) {
+    if (t == 0) {
+      // per-env parameters: their derived values before the tile is taken up - behind the re-issue the divisions' temporaries
+      // are live together with the lane's row, which cost the float64 instances a wave per SIMD (tank, N = 20: 138 VGPRs
+      // against 128)
+      if constexpr (!OUT) {
+        if (env_pars) pre_env = Sys::template prepare<real>(pn);
+      }
+      if (adopt_early) adopt_regs();
     }
     // 2. tile g has landed -> my row into registers (vmcnt retires in issue order: everything requested so far)
+    if constexpr (RCG_DMA_PRIO > 0 && ESZ == 8) __builtin_amdgcn_s_setprio(RCG_DMA_PRIO);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     real rows[RPL][R];  // the lane's rows: lane, lane + 64, ... of the tile
 #pragma unroll
@@ -365,6 +533,11 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
       } else {
         issue_tile(envb + (size_t)(t + 1) * TILE, rows_of(t + 1));
       }
+    }
+    if constexpr (RCG_DMA_PRIO > 0 && ESZ == 8) __builtin_amdgcn_s_setprio(0);
+    if (t == 0) {
+      if (!adopt_early) adopt_regs();
+      adopt_rest();
     }
 
     // 4. _actor_cost of this lane's rows (controllers.py:1284-1326), registers only, in candidate order
@@ -387,7 +560,7 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
       real J = 0, gk = 1;
       real S[NCHI];
 #pragma unroll
-      for (int i = 0; i < NCHI; ++i) S[i] = 0;
+      for (int i = 0; i < NCHI; ++i) S[i] = (PFX && G1 && i < DY) ? Sini[i < DY ? i : 0] : (real)0;
       real Phi[SQL ? DCMAX : 1];  // SQL: the regressor summed over the horizon (J = sum_k w . phi_k = w . sum_k phi_k)
 #pragma unroll
       for (int i = 0; i < (SQL ? DCMAX : 1); ++i) Phi[i] = 0;
@@ -400,10 +573,23 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
         for (int kk = 0; kk < N; ++kk) {
           if (kk > 0) {
             real d[DS];
-            Sys::template rhs<real, true>(pre_env, x, &cur[(kk - 1) * DU], d);  // unclipped: sys_rhs([], state, u[k-1])
+            // unclipped: sys_rhs([], state, u[k-1]); the first two steps with the env's shared trig where it has one
+            if constexpr (TRIG0 || TRIG1) {
+              if (kk == 1 && TRIG0)
+                Sys::template rhs_trig<real>(pre_env, x, &cur[(kk - 1) * DU], trig0[0], trig0[1], d);
+              else if (kk == 2 && TRIG1)
+                Sys::template rhs_trig<real>(pre_env, x, &cur[(kk - 1) * DU], trig1[0], trig1[1], d);
+              else
+                Sys::template rhs<real, true>(pre_env, x, &cur[(kk - 1) * DU], d);
+            } else {
+              Sys::template rhs<real, true>(pre_env, x, &cur[(kk - 1) * DU], d);
+            }
 #pragma unroll
             for (int c = 0; c < DS; ++c) {
-              x[c] = fma_r(h, d[c], x[c]);
+              if (PFX && kk == 1 && ((FREE >> c) & 1u))
+                x[c] = x1s[c];  // the env's (the same fma on the same operands, done once)
+              else
+                x[c] = fma_r(h, d[c], x[c]);
               if constexpr (!OUT) y[c] = x[c];  // no output map: y = x
             }
             if constexpr (OUT) sys_out<Sys, real, true>(pre_env, x, y);  // observation_sqn[k] = sys_out(state)
@@ -415,7 +601,11 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
           for (int c = 0; c < DU; ++c) chi[DY + c] = cur[kk * DU + c];
           if (G1) {
 #pragma unroll
-            for (int i = 0; i < NCHI; ++i) S[i] = fma_r(chi[i], chi[i], S[i]);
+            for (int i = 0; i < NCHI; ++i) {
+              // (PFX: S starts from the env's terms of y_0 and of the action-free components of y_1)
+              if (PFX && i < DY && (kk == 0 || (kk == 1 && ((FREE >> i) & 1u)))) continue;
+              S[i] = fma_r(chi[i], chi[i], S[i]);
+            }
           } else if (SQL) {
             critic_phi_accum<DY, DU, real>(chi, y, &cur[kk * DU], Phi, CS);
           } else if (RQL && kk == N - 1) {

@@ -34,15 +34,25 @@ struct Sys3WRobot {
   __device__ __forceinline__ static Pre<real> bcast(const Pre<real>& q, int l) {
     return {readlane_r(q.inv_m, l), readlane_r(q.inv_I, l)};
   }
-  template <typename real, bool HW = false>
-  __device__ __forceinline__ static void rhs(const Pre<real>& q, const real* x, const real* u, real* d) {
-    real s, c;
-    sincos_sel<real, HW>(x[2], &s, &c);
+  // (optional hook, k_actor_dma's shared rollout prefix) PFX_FREE: the components of f(x, u) that do not involve u - the first
+  // Euler step moves them alike for every candidate of an env; PFX_HEADING: the component whose trig the right-hand side
+  // takes (-1: none); rhs_trig: the right-hand side with that trig supplied - rhs() is sincos + rhs_trig, so a caller
+  // that holds the trig already runs the same operations on the same operands
+  static constexpr unsigned PFX_FREE = 0x7u;  // x, y and alpha follow (alpha, v, omega) alone
+  static constexpr int PFX_HEADING = 2;
+  template <typename real>
+  __device__ __forceinline__ static void rhs_trig(const Pre<real>& q, const real* x, const real* u, real s, real c, real* d) {
     d[0] = x[3] * c;
     d[1] = x[3] * s;
     d[2] = x[4];
     d[3] = q.inv_m * u[0];  // 1/m * action[0]
     d[4] = q.inv_I * u[1];  // 1/I * action[1]
+  }
+  template <typename real, bool HW = false>
+  __device__ __forceinline__ static void rhs(const Pre<real>& q, const real* x, const real* u, real* d) {
+    real s, c;
+    sincos_sel<real, HW>(x[2], &s, &c);
+    rhs_trig<real>(q, x, u, s, c, d);
   }
   // (A^T lam, B^T lam), A = d f/d x, B = d f/d u at (x, u): the adjoint sweep of k_actor_opt
   template <typename real, bool HW = false>
@@ -76,6 +86,9 @@ struct Sys3WRobotNI {
   __device__ __forceinline__ static Pre<real> bcast(const Pre<real>&, int) {
     return {};
   }
+  // (no rollout-prefix hook: every component of f involves the action, so only sincos(alpha_0) - one of the horizon's N - 1 -
+  // could be shared, and carrying it cost the float64 instances 21 VGPRs: rows of 12 - 16 reals fell from 4 waves per SIMD
+  // to 3, where the launcher wants 4 blocks per CU)
   template <typename real, bool HW = false>
   __device__ __forceinline__ static void rhs(const Pre<real>&, const real* x, const real* u, real* d) {
     real s, c;
@@ -103,6 +116,9 @@ struct Sys2Tank {
   static constexpr bool TGT = true;  // main_2tank.py:211: observation_target = [0.5, 0.5]
   static constexpr unsigned ZW_PRESET = 0u;  // R1 = diag[10, 10, 1]: every term counts
   static constexpr unsigned SHARED_U1 = 0;  // one input
+  // (no rollout-prefix hook: h2's first step does not involve u, but the rollouts leave this right-hand side's fusions to the
+  // compiler, per call site, so hoisting it could move bits; the cost terms of y_0 alone are two fmas, and carrying them
+  // cost the float64 instances a wave per SIMD)
   template <typename real>
   struct Pre {
     real inv_tau1, inv_tau2, K1, K2, K3;
