@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 121 /* 120 + output maps y = out(x) of registered systems: rcg_system_output_info, rcg_out */
+#define RCG_VERSION 122 /* 121 + RQL / SQL on registered systems (policy member CRITIC): rcg_system_has_critic, rcg_system_programs, rcg_critic_fit */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -191,8 +191,16 @@ int rcg_device_count(void);
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
  * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  rcg_create
- * refuses RQL / SQL and RCG_FLAG_DISTURB; the critic operators, the nominal controllers, rcg_actor_search,
- * rcg_control_ticks and rcg_loop_step return RCG_ERR_UNSUPPORTED with the handle untouched. */
+ * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_actor_search, rcg_control_ticks and rcg_loop_step return
+ * RCG_ERR_UNSUPPORTED with the handle untouched.
+ * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
+ * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
+ * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
+ * over [y - target, u] (quad-mix over the raw y), so W_CRITIC has dim_critic(structure, DY, du) rows and OBS_BUF holds
+ * observations [buffer_size][DY][B]; a tick pushes out(STATE).  The critic kernels are compiled the first time a handle needs
+ * them (one program per element type, critic structure and fit form), before the call enqueues anything; a split tick
+ * (rcg_set_tick_parts 2) is RCG_ERR_UNSUPPORTED for such a handle.  Without CRITIC rcg_create refuses RQL / SQL and the critic
+ * operators return RCG_ERR_UNSUPPORTED, as above. */
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
@@ -203,6 +211,13 @@ int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32
 /* output map of a built-in or registered system: dim_output, whether the policy defines out and out_jac_T (built-ins: ds, 0, 0);
  * any pointer may be NULL.  RCG_ERR_BAD_ARG for an id that names no system. */
 int rcg_system_output_info(int32_t sys_id, int32_t* dy, int32_t* has_out, int32_t* has_out_jac);
+/* whether a system runs the critic modes: 1 for the built-in ones and for a registered policy with CRITIC = true, else 0.
+ * RCG_ERR_BAD_ARG for an id that names no system. */
+int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic);
+/* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
+ * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs).  Writes at
+ * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
+int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 
 /* ---- life cycle: System.__init__ (systems.py:69-145), Simulator.__init__ (simulator.py:71-154),
  *      CtrlOptPred.__init__ (controllers.py:811-1044) ------------------------------------------ */
@@ -461,6 +476,9 @@ int rcg_control_tick_nominal(rcg_handle* h, double ctrl_gain, const double* ctrl
  * into the buffers and, if do_fit != 0, refit W_CRITIC by bounded least squares on the TD stack of
  * _critic_cost (replacement of _critic_optimizer, controllers.py:1248-1271); W_PREV := W_CRITIC. */
 int rcg_critic_update(rcg_handle* h, int32_t do_fit);
+/* The fit of rcg_critic_update alone, on OBS_BUF / ACT_BUF / W_PREV as they are (no push): for a caller that keeps the buffers
+ * itself and whose newest row - an observation [dy] of a system with an output map - is not a state it could set. */
+int rcg_critic_fit(rcg_handle* h);
 /* Episode boundary (Simulator.reset, simulator.py:197-204; CtrlOptPred.reset, controllers.py:1046):
  * RETURNS := ACCUM; ACCUM := 0; STATE := STATE_INIT; ACTION := action_init; STEP_IDX := 0;
  * EPISODE_IDX += 1.  Critic weights and buffers are retained, as in the reference. */

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librcg.so")
 
 # ---- enums (include/rcg.h) -------------------------------------------------------------------
-RCG_VERSION = 121
+RCG_VERSION = 122
 OK, ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_NONFINITE = 0, -1, -2, -3, -4, -5
 SYS_3WROBOT, SYS_3WROBOT_NI, SYS_2TANK = 0, 1, 2
 MODE_MPC, MODE_RQL, MODE_SQL = 0, 1, 2
@@ -54,6 +54,7 @@ SYMBOLS = [
     "rcg_profile_samples", "rcg_last_launch", "rcg_kernel_name", "rcg_wait_stream", "rcg_nominal_theta", "rcg_set_optimizer", "rcg_set_optimizer_tol", "rcg_set_tick_parts", "rcg_join", "rcg_loop_step", "rcg_loop_step_begin", "rcg_loop_step_end",
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
+    "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit",
 ]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
@@ -186,6 +187,9 @@ def lib():
         "rcg_system_info": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "rcg_system_output_info": (C.c_int, [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
         "rcg_out": (C.c_int, [vp, vp, vp, i32]),
+        "rcg_system_has_critic": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_critic_fit": (C.c_int, [vp]),
+        "rcg_system_programs": (C.c_int, [i32, C.c_char_p, i64, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name)  # AttributeError here = the .so does not export what rcg.h declares
@@ -209,9 +213,10 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac"}``: the id to put in ``rcg_cfg.sys_id``
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic"}``: the id to put in ``rcg_cfg.sys_id``
     (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
-    optimiser), its dim_output ``DY`` and whether it defines the output map ``out`` and its adjoint ``out_jac_T``.  ``SYS_DIMS``
+    optimiser), its dim_output ``DY``, whether it defines the output map ``out`` and its adjoint ``out_jac_T``, and whether it opts
+    in to the critic kernels (``CRITIC``: RQL / SQL).  ``SYS_DIMS``
     (``(ds, du, np)``) and ``SYS_DY`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
     the dimension limits)."""
     import time
@@ -229,8 +234,22 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     dy, has_out, has_out_jac = C.c_int32(0), C.c_int32(0), C.c_int32(0)
     check(L.rcg_system_output_info(sid.value, C.byref(dy), C.byref(has_out), C.byref(has_out_jac)))
     SYS_DY[sid.value] = dy.value
+    crit = C.c_int32(0)
+    check(L.rcg_system_has_critic(sid.value, C.byref(crit)))
     return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
-            "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value)}
+            "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value),
+            "has_critic": bool(crit.value)}
+
+
+def system_programs(sys_id: int) -> list:
+    """``[(program, name expression), ...]`` of everything compiled for a registered system so far (rcg_system_programs): the
+    two core programs of the registration, then the instances compiled on first use."""
+    L = lib()
+    need = C.c_int64(0)
+    check(L.rcg_system_programs(int(sys_id), None, 0, C.byref(need)))
+    buf = C.create_string_buffer(max(int(need.value), 1))
+    check(L.rcg_system_programs(int(sys_id), buf, len(buf), None))
+    return [tuple(line.split("\t", 1)) for line in buf.value.decode().splitlines() if line]
 
 
 def sys_dy(sys_id: int) -> int:

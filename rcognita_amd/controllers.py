@@ -67,14 +67,17 @@ class CtrlOptPred:
                 "sys_rhs must be the bound `_state_dyn` of a rcognita_amd System: arbitrary Python models cannot "
                 "run on the native path and there is no CPU fallback")
         self.sys = sys_obj
-        # a system compiled at run time (System.hip_policy) runs MPC: no critic kernels, no device search, the optimiser only
-        # when the policy has jac_T (and out_jac_T, if it has an output map)
+        # a system compiled at run time (System.hip_policy): RQL / SQL when its policy opts in to the critic kernels
+        # (`static constexpr bool CRITIC = true;`), no device search, the optimiser only when the policy has jac_T (and
+        # out_jac_T, if it has an output map)
         info = type(sys_obj)._hip_info if type(sys_obj).hip_policy is not None else None
         self._runtime_sys = info is not None
+        self._has_out = bool(info is not None and info.get("has_out"))
         if info is not None:
-            if mode != "MPC":
+            if mode != "MPC" and not info.get("has_critic"):
                 raise NotImplementedError(f"{type(sys_obj).__name__} is compiled from hip_policy: mode {mode!r} needs the critic "
-                                          "kernels, which exist for the built-in systems only; use mode='MPC'")
+                                          "kernels, which a policy opts in to with `static constexpr bool CRITIC = true;` "
+                                          "(the built-in systems have them); use mode='MPC'")
             has_opt = info["has_jac"] and (not info.get("has_out") or info.get("has_out_jac"))
             if candidates is None and (actor_opt == "sampling" or not has_opt):
                 raise NotImplementedError(
@@ -379,6 +382,11 @@ class CtrlOptPred:
     def _critic_optimizer(self):
         """Replacement of rcognita/controllers.py:1248-1271: native bounded least squares on the TD stack
         of the CURRENT buffers (no push)."""
+        if self._has_out:  # an output map: the newest row is an observation y = out(x), not a state the push could observe
+            self._sync_critic_state()
+            self._eng.critic_fit()
+            w = self._eng.get_field(N.FIELD_W_CRITIC).astype(float)
+            return w if self._batched else w[0]
         # rcg_critic_update pushes (ACTION, STATE) before it fits: upload the rows pre-shifted so that the push restores
         # them (the values travel through the handle's element type exactly as set_field + get_field would round them)
         ob = np.broadcast_to(self.observation_buffer, (self.B,) + self.observation_buffer.shape[-2:]).astype(self._eng.real)

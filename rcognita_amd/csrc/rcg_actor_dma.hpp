@@ -219,9 +219,9 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   constexpr bool GENR = V >= DMA_RQL_GEN_0;  // RQL whose stage cost is not the presets' diagonal quadratic one: stage_any per step
   static_assert(!(GEN || GENR) || TGT, "the generic-cost instances subtract a target (zeros for a handle without one)");
   constexpr int CS = dma_cs(V);  // compile-time critic structure
-  constexpr int DCMAX = CRIT ? dma_dc(CS, DS, DU) : 1;
+  constexpr int DCMAX = CRIT ? dma_dc(CS, DY, DU) : 1;
   constexpr int ESZ = (int)sizeof(real);
-  constexpr int WSLOT = dma_wslot(ESZ, V, DS, DU);  // > 0: critic weights in LDS (instances with more than 9 of them)
+  constexpr int WSLOT = dma_wslot(ESZ, V, DY, DU);  // > 0: critic weights in LDS (instances with more than 9 of them)
   constexpr bool WLDS = WSLOT > 0;
   constexpr int WREG = WLDS ? 1 : DCMAX;             // register copies of the weights (current env, next env)
   static_assert(R % DU == 0 && R >= DU && R <= 40, "row = N*du reals, at most 40 (f32: 160 bytes, f64: 320)");

@@ -75,7 +75,7 @@ __global__ __launch_bounds__(256) void k_actor_dma_packed(const ActorArgs<real> 
   constexpr bool OUT = HasOut<Sys>::value;  // an output map (registered systems only); else y = x
   constexpr bool G1 = V == DMA_MPC_G1, SQL = V >= DMA_SQL_0, RQL = V >= DMA_RQL_0 && !SQL, CRIT = RQL || SQL;
   constexpr int CS = SQL ? V - DMA_SQL_0 : (RQL ? V - DMA_RQL_0 : 0);  // compile-time critic structure
-  constexpr int DC = CRIT ? dma_dc(CS, DS, DU) : 1;
+  constexpr int DC = CRIT ? dma_dc(CS, DY, DU) : 1;
   constexpr int ESZ = (int)sizeof(real);
   static_assert(!CRIT || packed_critic_ok(DC, ESZ), "per-lane critic weights: at most 36 dwords");
   static_assert(R % DU == 0 && R >= DU && R <= 40, "row = N*du reals, at most 40");

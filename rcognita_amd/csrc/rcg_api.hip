@@ -225,8 +225,13 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   if (cfg->critic_struct < 0 || cfg->critic_struct > 3)
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad critic_struct");
   const int ds = rtc ? rd.ds : kDims[cfg->sys_id][0], du = rtc ? rd.du : kDims[cfg->sys_id][1], np = rtc ? rd.np : kDims[cfg->sys_id][2];
-  if (rtc && cfg->mode != RCG_MODE_MPC)
+  // (a policy opts in to the critic kernels with `static constexpr bool CRITIC = true`, rcg.h)
+  if (rtc && cfg->mode != RCG_MODE_MPC && !rd.has_critic)
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time runs MPC only (no RQL / SQL critic kernels)");
+  // the critic's regressor is over [y, u]: its weights must fit w_init / w_min / w_max and the fit kernels' 64-bit variable masks
+  if (dim_critic(cfg->critic_struct, rtc ? rd.dy : ds, du) > RCG_MAX_DC)
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: dim_critic %d (dim_output %d, dim_input %d) beyond the limit %d",
+                    dim_critic(cfg->critic_struct, rtc ? rd.dy : ds, du), rtc ? rd.dy : ds, du, RCG_MAX_DC);
   if (rtc && (cfg->flags & RCG_FLAG_DISTURB))
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time has no disturbance model");
   // (the reference's horizon is unbounded, controllers.py:965.  Rows of up to RCG_MAX_ROW reals are staged in LDS tiles; longer
@@ -702,6 +707,17 @@ int rcg_critic_update(rcg_handle* h, int32_t do_fit) {
   return h->sys->critic_update(h, 0, 1, do_fit ? 1 : 0);
 }
 
+// the fit alone, on the buffers as they are: what a caller that keeps the buffers itself needs when the row a push appends -
+// the observation of STATE - is not a row it can hand over as a state (an output map with dim_output != dim_state)
+int rcg_critic_fit(rcg_handle* h) {
+  DeviceGuard dev_guard(h);
+  if (!h) return RCG_ERR_BAD_ARG;
+  if (!h->f[RCG_FIELD_OBS_BUF])
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_critic_fit: handle has no critic buffers (buffer_size = 0)");
+  if (h->cfg.n_critic - 1 < 1) return critic_keep_init(h);  // empty TD stack: the (clipped) initial guess
+  return h->sys->critic_update(h, 0, 0, 1);
+}
+
 // Argument checks of the decision step, made BEFORE the tick mutates anything (env step, buffer push): a refused
 // call leaves the handle exactly as it was.
 static int check_candidates(rcg_handle* h, const char* who, const void* cand, int32_t K) {
@@ -739,6 +755,7 @@ static int tick_critic_phase(rcg_handle* h, const char* who) {
 // rows), and enough envs for two launches to be worth it (rcg_set_tick_parts).
 static bool tick_splits(rcg_handle* h, const void* cand, int32_t K) {
   if (h->tick_parts == 1 || h->cfg.mode == RCG_MODE_MPC || !cand) return false;
+  if (h->rtc) return false;  // (a system registered at run time never splits by itself; an explicit split is refused, below)
   // automatic: only on a stream the handle OWNS (rcg_use_own_stream).  On a caller's stream (rcg_set_stream) or the null stream
   // the caller may enqueue its own work behind the tick - a kernel reading rcg_field_ptr(ACTION) - and that work must find the
   // tick finished: a split tick returns with half the batch on internal streams the caller's stream does not wait for
@@ -783,6 +800,18 @@ int rcg_control_tick(rcg_handle* h, const void* cand, int32_t K) {
   if (rc) {
     join_split(h);
     return rc;
+  }
+  if (h->rtc && h->cfg.mode != RCG_MODE_MPC) {
+    // a registered system's RQL / SQL tick runs whole: the explicit split is refused, and every instance the tick needs is
+    // resolved (compiled on first use) here - before the env step and the push - so that a refusal leaves the handle as it was
+    if (h->tick_parts == 2 && cand)
+      rc = rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick: no split tick (rcg_set_tick_parts 2) for a system registered at run time");
+    else
+      rc = rtc_prepare_tick(h, cand, K);
+    if (rc) {
+      join_split(h);
+      return rc;
+    }
   }
   if (tick_splits(h, cand, K)) {
     rc = split_streams(h);
@@ -946,6 +975,10 @@ int rcg_control_tick_opt(rcg_handle* h, int32_t iters, int32_t warm_start) {
   if (!h || iters < 0) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_control_tick_opt: iters must be >= 0");
   int rc = check_optimizer(h, "rcg_control_tick_opt");
   if (rc) return rc;
+  if (h->rtc && h->cfg.mode != RCG_MODE_MPC) {  // (refusals and the critic program before the critic phase enqueues anything)
+    rc = rtc_prepare_tick_opt(h);
+    if (rc) return rc;
+  }
   bool sim_first = true;  // MPC: the env step of the tick is issued by the optimiser's launcher
   if (h->cfg.mode != RCG_MODE_MPC) {  // RQL/SQL: env step + buffer push + critic fit come first (one launch)
     rc = tick_critic_phase(h, "rcg_control_tick_opt");
@@ -1107,6 +1140,9 @@ int rcg_control_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t wa
   if (!h) return RCG_ERR_BAD_ARG;
   int rc = check_search(h, "rcg_control_tick_search", K, rounds);
   if (rc) return rc;
+  // (no device search for a system registered at run time: refused here, before the critic phase of an RQL / SQL tick runs)
+  if (h->rtc)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_search: not available for a system registered at run time");
   bool sim_first = true;
   if (h->cfg.mode != RCG_MODE_MPC) {
     rc = tick_critic_phase(h, "rcg_control_tick_search");

@@ -104,7 +104,8 @@ struct FitArgs {
 template <typename Sys, typename real, int CS, int MAXM, typename RowSink>
 __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
                                                      const long b, const bool store, double (&bv)[MAXM], RowSink row) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, DC = CriticDim<CS, DS, DU>::value;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, DC = CriticDim<CS, DY, DU>::value;
+  constexpr bool OUT = HasOut<Sys>::value;  // the buffers hold observations y = out(x): [buffer_size][DY][B]
   // rows of the shifted buffers that stay in registers for the TD stack: new row r = old row r + 1, r = 0 .. KEEP - 1
   constexpr int KEEP = MAXM + 1 <= 4 ? MAXM + 1 : 4;
   const long B = P.B;
@@ -119,7 +120,7 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
 #pragma unroll
     for (int i = 0; i < DC; ++i) wpr[i] = F.w_prev[(long)i * B + b];
   }
-  real ko[KEEP][DS], ka[KEEP][DU];  // do_push: old rows 1 .. KEEP (= new rows 0 .. KEEP - 1); else rows 0 .. KEEP - 1
+  real ko[KEEP][DY], ka[KEEP][DU];  // do_push: old rows 1 .. KEEP (= new rows 0 .. KEEP - 1); else rows 0 .. KEEP - 1
   const int koff = F.do_push ? 1 : 0;
   const int ring = F.ring;  // > 0: ring mode (with do_push)
   // physical row of the row that is logical row r once this call's push is done
@@ -133,7 +134,7 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
     if (k + koff < bs) {
       const int pr = ring ? phys(k) : k + koff;
 #pragma unroll
-      for (int c = 0; c < DS; ++c) ko[k][c] = F.obs_buf[((long)pr * DS + c) * B + b];
+      for (int c = 0; c < DY; ++c) ko[k][c] = F.obs_buf[((long)pr * DY + c) * B + b];
 #pragma unroll
       for (int c = 0; c < DU; ++c) ka[k][c] = F.act_buf[((long)pr * DU + c) * B + b];
     }
@@ -164,16 +165,24 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
         }
       }
     }
+    // what is pushed is the observation of the (new) state: y = out(x) as k_out and upd_accum_obj form it (identity without `out`)
+    real yb[OUT ? DY : 1];
+    const real* ys = xs;
+    if constexpr (OUT) {
+      const auto pre_o = load_pre<Sys, real>(Pr, F.sim.pars_env, b);
+      sys_out<Sys, real, false>(pre_o, xs, yb);
+      ys = yb;
+    }
     if (F.do_push && ring) {  // ring mode: the new row takes the oldest row's place, nothing else moves
 #pragma unroll
-      for (int c = 0; c < DS; ++c) if (store) F.obs_buf[((long)(ring - 1) * DS + c) * B + b] = xs[c];
+      for (int c = 0; c < DY; ++c) if (store) F.obs_buf[((long)(ring - 1) * DY + c) * B + b] = ys[c];
 #pragma unroll
       for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)(ring - 1) * DU + c) * B + b] = ua[c];
 #pragma unroll
       for (int k = 0; k < KEEP; ++k)
         if (k == bs - 1) {
 #pragma unroll
-          for (int c = 0; c < DS; ++c) ko[k][c] = xs[c];
+          for (int c = 0; c < DY; ++c) ko[k][c] = ys[c];
 #pragma unroll
           for (int c = 0; c < DU; ++c) ka[k][c] = ua[c];
         }
@@ -182,19 +191,19 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
       for (int k = 0; k < KEEP; ++k)
         if (k + 1 < bs) {
 #pragma unroll
-          for (int c = 0; c < DS; ++c) if (store) F.obs_buf[((long)k * DS + c) * B + b] = ko[k][c];
+          for (int c = 0; c < DY; ++c) if (store) F.obs_buf[((long)k * DY + c) * B + b] = ko[k][c];
 #pragma unroll
           for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)k * DU + c) * B + b] = ka[k][c];
         }
       // the rest of the shift four rows at a time, all loads of a pass before its stores
       constexpr int CH = 4;
       for (int r0 = KEEP; r0 < bs - 1; r0 += CH) {
-        real ro[CH][DS], ra[CH][DU];
+        real ro[CH][DY], ra[CH][DU];
 #pragma unroll
         for (int k = 0; k < CH; ++k)
           if (r0 + k < bs - 1) {
 #pragma unroll
-            for (int c = 0; c < DS; ++c) ro[k][c] = F.obs_buf[((long)(r0 + k + 1) * DS + c) * B + b];
+            for (int c = 0; c < DY; ++c) ro[k][c] = F.obs_buf[((long)(r0 + k + 1) * DY + c) * B + b];
 #pragma unroll
             for (int c = 0; c < DU; ++c) ra[k][c] = F.act_buf[((long)(r0 + k + 1) * DU + c) * B + b];
           }
@@ -202,20 +211,20 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
         for (int k = 0; k < CH; ++k)
           if (r0 + k < bs - 1) {
 #pragma unroll
-            for (int c = 0; c < DS; ++c) if (store) F.obs_buf[((long)(r0 + k) * DS + c) * B + b] = ro[k][c];
+            for (int c = 0; c < DY; ++c) if (store) F.obs_buf[((long)(r0 + k) * DY + c) * B + b] = ro[k][c];
 #pragma unroll
             for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)(r0 + k) * DU + c) * B + b] = ra[k][c];
           }
       }
 #pragma unroll
-      for (int c = 0; c < DS; ++c) if (store) F.obs_buf[((long)(bs - 1) * DS + c) * B + b] = xs[c];
+      for (int c = 0; c < DY; ++c) if (store) F.obs_buf[((long)(bs - 1) * DY + c) * B + b] = ys[c];
 #pragma unroll
       for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)(bs - 1) * DU + c) * B + b] = ua[c];
 #pragma unroll
       for (int k = 0; k < KEEP; ++k)
         if (k == bs - 1) {  // (buffer_size <= KEEP: the row just pushed is one of the kept rows)
 #pragma unroll
-          for (int c = 0; c < DS; ++c) ko[k][c] = xs[c];
+          for (int c = 0; c < DY; ++c) ko[k][c] = ys[c];
 #pragma unroll
           for (int c = 0; c < DU; ++c) ka[k][c] = ua[c];
         }
@@ -229,24 +238,24 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
 #pragma unroll
   for (int r = 0; r <= MAXM; ++r) {
     if (r <= m) {
-      double y[DS], u[DU], chi[NCHI], phi[DC];
+      double y[DY], u[DU], chi[NCHI], phi[DC];
       if (r < KEEP) {
 #pragma unroll
-        for (int c = 0; c < DS; ++c) y[c] = (double)ko[r][c];
+        for (int c = 0; c < DY; ++c) y[c] = (double)ko[r][c];
 #pragma unroll
         for (int c = 0; c < DU; ++c) u[c] = (double)ka[r][c];
       } else {  // m > 3: beyond the kept rows (written above by this lane: same-address order, served by L2)
         const int pr = phys(r);
 #pragma unroll
-        for (int c = 0; c < DS; ++c) y[c] = (double)F.obs_buf[((long)pr * DS + c) * B + b];
+        for (int c = 0; c < DY; ++c) y[c] = (double)F.obs_buf[((long)pr * DY + c) * B + b];
 #pragma unroll
         for (int c = 0; c < DU; ++c) u[c] = (double)F.act_buf[((long)pr * DU + c) * B + b];
       }
       if (P.has_target)
-        make_chi<DS, DU, true, double>(P, y, u, chi);
+        make_chi<DY, DU, true, double>(P, y, u, chi);
       else
-        make_chi<DS, DU, false, double>(P, y, u, chi);
-      critic_phi<CS, DS, DU>(chi, y, u, phi);
+        make_chi<DY, DU, false, double>(P, y, u, chi);
+      critic_phi<CS, DY, DU>(chi, y, u, phi);
       if (r > 0) {  // gamma * w_prev . phi(row r) belongs to TD row r - 1
         double q = 0.0;
 #pragma unroll
@@ -267,11 +276,11 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
 template <typename Sys, typename real, int CS, int MAXM>
 __device__ __forceinline__ bool critic_prologue(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
                                                 const long b, const bool store,
-                                                double (&A)[MAXM][CriticDim<CS, Sys::DS, Sys::DU>::value], double (&bv)[MAXM],
-                                                double (&w0)[CriticDim<CS, Sys::DS, Sys::DU>::value],
-                                                double (&lo)[CriticDim<CS, Sys::DS, Sys::DU>::value],
-                                                double (&hi)[CriticDim<CS, Sys::DS, Sys::DU>::value]) {
-  constexpr int DC = CriticDim<CS, Sys::DS, Sys::DU>::value;
+                                                double (&A)[MAXM][CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value], double (&bv)[MAXM],
+                                                double (&w0)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value],
+                                                double (&lo)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value],
+                                                double (&hi)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value]) {
+  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
 #pragma unroll
   for (int r = 0; r < MAXM; ++r)
 #pragma unroll
@@ -294,7 +303,7 @@ __device__ __forceinline__ bool critic_prologue(const FitArgs<real>& F, const KP
 // pushes mod buffer_size, in place (cycle by cycle; all components of a row travel together), by the lane that stored them.
 template <typename Sys, typename real>
 __device__ __forceinline__ void critic_ring_unrotate(const FitArgs<real>& F, const KParams<real>& Pr, const long b, const int pushes) {
-  constexpr int DS = Sys::DS, DU = Sys::DU;
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU;
   const long B = Pr.B;
   const int bs = Pr.buffer_size, sh = pushes % bs;
   if (sh == 0) return;
@@ -305,9 +314,9 @@ __device__ __forceinline__ void critic_ring_unrotate(const FitArgs<real>& F, con
     r = q;
   }
   for (int s = 0; s < g; ++s) {
-    real to[DS], ta[DU];
+    real to[DY], ta[DU];
 #pragma unroll
-    for (int c = 0; c < DS; ++c) to[c] = F.obs_buf[((long)s * DS + c) * B + b];
+    for (int c = 0; c < DY; ++c) to[c] = F.obs_buf[((long)s * DY + c) * B + b];
 #pragma unroll
     for (int c = 0; c < DU; ++c) ta[c] = F.act_buf[((long)s * DU + c) * B + b];
     int j = s;
@@ -315,19 +324,19 @@ __device__ __forceinline__ void critic_ring_unrotate(const FitArgs<real>& F, con
       int nx = j + sh;
       if (nx >= bs) nx -= bs;
       if (nx == s) break;
-      real vo[DS], va[DU];
+      real vo[DY], va[DU];
 #pragma unroll
-      for (int c = 0; c < DS; ++c) vo[c] = F.obs_buf[((long)nx * DS + c) * B + b];
+      for (int c = 0; c < DY; ++c) vo[c] = F.obs_buf[((long)nx * DY + c) * B + b];
 #pragma unroll
       for (int c = 0; c < DU; ++c) va[c] = F.act_buf[((long)nx * DU + c) * B + b];
 #pragma unroll
-      for (int c = 0; c < DS; ++c) F.obs_buf[((long)j * DS + c) * B + b] = vo[c];
+      for (int c = 0; c < DY; ++c) F.obs_buf[((long)j * DY + c) * B + b] = vo[c];
 #pragma unroll
       for (int c = 0; c < DU; ++c) F.act_buf[((long)j * DU + c) * B + b] = va[c];
       j = nx;
     }
 #pragma unroll
-    for (int c = 0; c < DS; ++c) F.obs_buf[((long)j * DS + c) * B + b] = to[c];
+    for (int c = 0; c < DY; ++c) F.obs_buf[((long)j * DY + c) * B + b] = to[c];
 #pragma unroll
     for (int c = 0; c < DU; ++c) F.act_buf[((long)j * DU + c) * B + b] = ta[c];
   }
@@ -338,7 +347,7 @@ __device__ __forceinline__ void critic_ring_unrotate(const FitArgs<real>& F, con
 template <typename Sys, typename real, int CS, int MAXM>
 __device__ __forceinline__ void critic_update_env(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
                                                   const long b) {
-  constexpr int DC = CriticDim<CS, Sys::DS, Sys::DU>::value;
+  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
   const long B = P.B;
   const int m = P.n_critic - 1;  // rows of the TD stack, 1 <= m <= MAXM (checked on the host)
   double A[MAXM][DC], bv[MAXM], w0[DC], lo[DC], hi[DC];

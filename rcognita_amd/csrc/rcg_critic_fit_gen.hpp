@@ -21,7 +21,7 @@ __host__ __device__ constexpr long fit_gen_scratch_doubles(int m, int dc) { retu
 template <typename Sys, typename real, int CS>
 __global__ __launch_bounds__(64) void k_critic_fit_gen(const FitArgs<real> F, const KParams<double> P, const KParams<real> Pr,
                                                        double* const S) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, DC = CriticDim<CS, DS, DU>::value;
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, DC = CriticDim<CS, DY, DU>::value;
   const long b = F.env_lo + (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (F.env_hi > 0 ? (long)F.env_hi : P.B)) return;
   const long B = P.B;
@@ -53,16 +53,16 @@ __global__ __launch_bounds__(64) void k_critic_fit_gen(const FitArgs<real> F, co
 #pragma unroll
     for (int i = 0; i < DC; ++i) wp[i] = (double)F.w_prev[(long)i * B + b];
     for (int r = 0; r <= m; ++r) {
-      double y[DS], u[DU], chi[NCHI], phi[DC];
+      double y[DY], u[DU], chi[NCHI], phi[DC];
 #pragma unroll
-      for (int c = 0; c < DS; ++c) y[c] = (double)F.obs_buf[((long)r * DS + c) * B + b];
+      for (int c = 0; c < DY; ++c) y[c] = (double)F.obs_buf[((long)r * DY + c) * B + b];
 #pragma unroll
       for (int c = 0; c < DU; ++c) u[c] = (double)F.act_buf[((long)r * DU + c) * B + b];
       if (P.has_target)
-        make_chi<DS, DU, true, double>(P, y, u, chi);
+        make_chi<DY, DU, true, double>(P, y, u, chi);
       else
-        make_chi<DS, DU, false, double>(P, y, u, chi);
-      critic_phi<CS, DS, DU>(chi, y, u, phi);
+        make_chi<DY, DU, false, double>(P, y, u, chi);
+      critic_phi<CS, DY, DU>(chi, y, u, phi);
       if (r > 0) {  // gamma * w_prev . phi(row r) belongs to TD row r - 1
         double q = 0.0;
 #pragma unroll

@@ -53,7 +53,7 @@ __device__ __forceinline__ double quad_sum(double x) {
 template <typename Sys, typename real, int CS, int MAXM>
 __device__ __forceinline__ void critic_update_env_ml(const FitArgs<real>& F, const KParams<double>& P,
                                                      const KParams<real>& Pr, const long b, const int s) {
-  constexpr int DC = CriticDim<CS, Sys::DS, Sys::DU>::value;
+  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
   constexpr int NS = (DC + FIT_L - 1) / FIT_L;  // slots per lane
   const long B = P.B;
   const int m = P.n_critic - 1;

@@ -89,7 +89,7 @@ static bool launch_dma_packed_r(int r, int variant, dim3 grid, dim3 block, size_
 #define RCG_DMAP_CASE(V)                                                                                             \
   case V: {                                                                                                          \
     if constexpr ((V) >= DMA_RQL_0 &&                                                                                \
-                  !packed_critic_ok(dma_dc(((V) >= DMA_SQL_0 ? (V)-DMA_SQL_0 : (V)-DMA_RQL_0), Sys::DS, Sys::DU),    \
+                  !packed_critic_ok(dma_dc(((V) >= DMA_SQL_0 ? (V)-DMA_SQL_0 : (V)-DMA_RQL_0), sys_dy<Sys>(), Sys::DU), \
                                     (int)sizeof(real))) {                                                            \
       return false; /* too many weights for per-lane registers: no instance, the caller takes another kernel */      \
     } else {                                                                                                         \

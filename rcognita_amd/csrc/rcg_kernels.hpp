@@ -1348,36 +1348,36 @@ __global__ void k_out(const real* state, real* obs, const real* pars_env, long n
 
 template <typename Sys, typename real>
 __global__ void k_critic(const real* obs, const real* act, const real* w, real* out, long n, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;  // the regressor is over [y - target, u]
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  real y[DS], u[DU], chi[NCHI];
+  real y[DY], u[DU], chi[NCHI];
 #pragma unroll
-  for (int c = 0; c < DS; ++c) y[c] = obs[(long)c * n + i];
+  for (int c = 0; c < DY; ++c) y[c] = obs[(long)c * n + i];
 #pragma unroll
   for (int c = 0; c < DU; ++c) u[c] = act[(long)c * n + i];
   if (P.has_target)
-    make_chi<DS, DU, true, real>(P, y, u, chi);
+    make_chi<DY, DU, true, real>(P, y, u, chi);
   else
-    make_chi<DS, DU, false, real>(P, y, u, chi);
-  out[i] = critic_value<DS, DU, real>(P, chi, y, u, [&](int k) -> real { return w[(long)k * n + i]; });
+    make_chi<DY, DU, false, real>(P, y, u, chi);
+  out[i] = critic_value<DY, DU, real>(P, chi, y, u, [&](int k) -> real { return w[(long)k * n + i]; });
 }
 
 // _critic_cost (controllers.py:1216-1245) on the OLDEST Ncritic buffer rows, lane == env
 template <typename Sys, typename real>
 __global__ void k_critic_cost(const real* w, const real* w_prev, const real* obs_buf, const real* act_buf, real* Jc,
                               const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;  // the regressor is over [y - target, u]
   const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long B = P.B;
   if (b >= B) return;
   real acc = 0;
   for (int k = P.n_critic - 1; k >= 1; --k) {
-    real yp[DS], yn[DS], up[DU], un[DU], chip[NCHI], chin[NCHI];
+    real yp[DY], yn[DY], up[DU], un[DU], chip[NCHI], chin[NCHI];
 #pragma unroll
-    for (int c = 0; c < DS; ++c) {
-      yp[c] = obs_buf[((long)(k - 1) * DS + c) * B + b];
-      yn[c] = obs_buf[((long)k * DS + c) * B + b];
+    for (int c = 0; c < DY; ++c) {
+      yp[c] = obs_buf[((long)(k - 1) * DY + c) * B + b];
+      yn[c] = obs_buf[((long)k * DY + c) * B + b];
     }
 #pragma unroll
     for (int c = 0; c < DU; ++c) {
@@ -1385,15 +1385,15 @@ __global__ void k_critic_cost(const real* w, const real* w_prev, const real* obs
       un[c] = act_buf[((long)k * DU + c) * B + b];
     }
     if (P.has_target) {
-      make_chi<DS, DU, true, real>(P, yp, up, chip);
-      make_chi<DS, DU, true, real>(P, yn, un, chin);
+      make_chi<DY, DU, true, real>(P, yp, up, chip);
+      make_chi<DY, DU, true, real>(P, yn, un, chin);
     } else {
-      make_chi<DS, DU, false, real>(P, yp, up, chip);
-      make_chi<DS, DU, false, real>(P, yn, un, chin);
+      make_chi<DY, DU, false, real>(P, yp, up, chip);
+      make_chi<DY, DU, false, real>(P, yn, un, chin);
     }
-    const real cp = critic_value<DS, DU, real>(P, chip, yp, up, [&](int i) -> real { return w[(long)i * B + b]; });
+    const real cp = critic_value<DY, DU, real>(P, chip, yp, up, [&](int i) -> real { return w[(long)i * B + b]; });
     const real cn =
-        critic_value<DS, DU, real>(P, chin, yn, un, [&](int i) -> real { return w_prev[(long)i * B + b]; });
+        critic_value<DY, DU, real>(P, chin, yn, un, [&](int i) -> real { return w_prev[(long)i * B + b]; });
     const real e = cp - P.gamma * cn - stage_any<NCHI, real>(P, chip);
     acc += (real)0.5 * e * e;
   }

@@ -9,11 +9,14 @@
 //                    long-row form), k_actor_opt without LOOP when the policy has jac_T (and out_jac_T if it has out), k_out
 //                    when the policy has an output map `out` (DY = dim_output; every kernel then observes y = out(x));
 //   on first use     k_actor_dma / k_actor_dma_packed at the handle's row length and variant: one small program each, cached;
+//                    for a policy that opts in with `static constexpr bool CRITIC = true`, the critic program of a handle's
+//                    (element type, critic structure, fit form): k_critic, k_critic_cost and the fit kernel fit_plan picks;
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan (rcg_sysops.hpp), the functions
-// the built-in launchers use.  What is not compiled is refused with RCG_ERR_UNSUPPORTED before anything is enqueued: the critic
-// kernels, the nominal controllers, the device search, T ticks per launch and rcg_loop_step (rcg_create refuses RQL / SQL and
-// the disturbance model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
+// the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
+// RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC (rcg_create refuses RQL / SQL for
+// it), the nominal controllers, the device search, T ticks per launch and rcg_loop_step (rcg_create refuses the disturbance
+// model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
 // and a handle keeps the functions it has resolved; nothing is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
 
@@ -46,6 +49,8 @@ struct RtcSystem {
   bool tgt;                 // the policy's TGT (default false): which k_actor_dma instance serves a handle with a target
   RtcProgram core[2];       // [0] float, [1] double
   std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant)
+  std::map<std::tuple<int, int, int>, std::unique_ptr<RtcProgram>> critic;    // (f64, critic structure, FIT_FORM_*)
+  std::vector<std::string> compiled;  // "<program>\t<name expression>" of everything compiled so far (rcg_system_programs)
 };
 
 namespace {
@@ -71,7 +76,7 @@ bool is_identifier(const char* s) {
 
 // The generated unit: the kernel headers, the policy (its own file name and line numbers in hipRTC's log), the adapter that
 // supplies the optional members and the checks of the declared dimensions.
-std::string unit_source(const RtcSystem& S) {
+std::string unit_source(const RtcSystem& S, bool critic = false) {
   char dims[1536];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
@@ -81,7 +86,8 @@ std::string unit_source(const RtcSystem& S) {
            "but %s defines no out (without an output map the observation is the state)\");\n",
            S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str());
   const std::string& N = S.name;
-  return "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
+  return std::string(critic ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_critic_fit_gen.hpp\"\n" : "") +
+         "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
          "namespace rtc {\n"
@@ -100,7 +106,9 @@ std::string unit_source(const RtcSystem& S) {
          "template <class S> struct ojac<S, void_t<decltype(&S::template out_jac_T<float, true>)>> { static constexpr bool v = true; };\n"
          "template <class S, class = void> struct dy { static constexpr int v = S::DS; };\n"
          "template <class S> struct dy<S, void_t<decltype(S::DY)>> { static constexpr int v = S::DY; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC> __global__ void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct crit { static constexpr bool v = false; };\n"
+         "template <class S> struct crit<S, void_t<decltype(S::CRITIC)>> { static constexpr bool v = S::CRITIC; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -196,6 +204,23 @@ std::string expr_dma(bool packed, int R, int variant, bool sys_tgt) {
 }
 
 template <typename real>
+std::string expr_critic() {
+  return std::string("rcg::k_critic<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+template <typename real>
+std::string expr_critic_cost() {
+  return std::string("rcg::k_critic_cost<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+// the fit kernel of a form (rcg_sysops.hpp::fit_plan)
+template <typename real>
+std::string expr_fit(int cs, int form) {
+  const std::string head = std::string("<") + kSysExpr + ", " + real_name<real>() + ", " + std::to_string(cs);
+  if (form == FIT_FORM_GEN) return "rcg::k_critic_fit_gen" + head + ">";
+  if (form == FIT_FORM_3ML) return "rcg::k_critic_fit_ml" + head + ", 3>";
+  return "rcg::k_critic_fit" + head + ", " + std::to_string(form == FIT_FORM_3 ? 3 : kFitMaxRows) + ">";
+}
+
+template <typename real>
 std::vector<std::string> core_exprs(const RtcDims& d) {
   const bool has_jac = d.has_jac && (!d.has_out || d.has_out_jac);  // (the optimiser's adjoint needs both with an output map)
   std::vector<std::string> e{expr_rhs<real>(), expr_stage_obj<real>(), expr_sim<real>(false), expr_sim<real>(true)};
@@ -277,10 +302,71 @@ int dma_function(rcg_handle* h, bool packed, int R, int variant, hipFunction_t* 
   }
   std::lock_guard<std::mutex> lock(g_mu);
   auto it = S.dma.find(key);
-  if (it == S.dma.end()) it = S.dma.emplace(key, std::move(P)).first;  // (another thread may have published it meanwhile)
+  if (it == S.dma.end()) {  // (else another thread has published it meanwhile)
+    it = S.dma.emplace(key, std::move(P)).first;
+    S.compiled.push_back(S.name + "_dma.hip\t" + expr);
+  }
   const int rc = function(h, *it->second, expr, fn);
   if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
   return rc;
+}
+
+// The critic program of the handle's (element type, critic structure) and of fit form `form`: k_critic, k_critic_cost and that
+// form's fit kernel - compiled the first time a handle asks for it, as the k_actor_dma instances are, then cached.  Any of the
+// three out-pointers may be null.
+template <typename real>
+int critic_functions(rcg_handle* h, int form, hipFunction_t* f_critic, hipFunction_t* f_cost, hipFunction_t* f_fit) {
+  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
+  if (!S.dims.has_critic) return RCG_ERR_UNSUPPORTED;  // (the callers refuse by name first)
+  const int cs = h->cfg.critic_struct;
+  const std::string e[3] = {expr_critic<real>(), expr_critic_cost<real>(), expr_fit<real>(cs, form)};
+  hipFunction_t* const out[3] = {f_critic, f_cost, f_fit};
+  bool all = true;
+  for (int i = 0; i < 3; ++i) {
+    if (!out[i]) continue;
+    auto hit = h->rtc_fn.find(e[i]);
+    if (hit != h->rtc_fn.end())
+      *out[i] = hit->second;
+    else
+      all = false;
+  }
+  if (all) return RCG_OK;
+  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, cs, form);
+  bool have;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    have = S.critic.count(key) != 0;
+  }
+  const std::string file = S.name + "_critic.hip";
+  std::unique_ptr<RtcProgram> P;
+  if (!have) {
+    P.reset(new RtcProgram);
+    std::string log;
+    const int rc = compile(unit_source(S, true), file, {e[0], e[1], e[2]}, P.get(), &log);
+    if (rc) {
+      h->err = "runtime system " + S.name + ": compiling the critic program (" + e[2] + "): " + log;
+      return RCG_ERR_HIP;
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = S.critic.find(key);
+  if (it == S.critic.end()) {
+    it = S.critic.emplace(key, std::move(P)).first;
+    for (const auto& x : e) S.compiled.push_back(file + "\t" + x);
+  }
+  for (int i = 0; i < 3; ++i) {
+    if (!out[i]) continue;
+    const int rc = function(h, *it->second, e[i], out[i]);
+    if (rc) return rc;
+    h->rtc_fn[e[i]] = *out[i];
+  }
+  return RCG_OK;
+}
+
+int refuse_critic(rcg_handle* h, const char* who) {
+  return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                  "%s: not available for a system registered at run time whose policy does not opt in with CRITIC (%s)", who,
+                  h->rtc ? h->rtc->name.c_str() : "?");
 }
 
 // one launch on the handle's stream; inside a due ProfScope it carries the scope's event pair (rcg_profile)
@@ -356,6 +442,22 @@ int rtc_sim_step(rcg_handle* h, int32_t n_substeps) {
   return by_dtype(h, [&](auto r) { return sim_step<decltype(r)>(h, n_substeps); });
 }
 
+// The instance that serves a plan: which of the three decision kernels, and its function (compiled on first use).  Shared by the
+// launcher below and by rtc_prepare_tick, which resolves a tick's instance before the tick enqueues anything.
+// (the packed RQL / SQL variants have an instance only while the critic weights fit a lane's registers, packed_critic_ok: beyond
+// that the shape goes on to k_actor_dma / k_actor, as launch_actor's does when launch_dma_packed finds no instance)
+struct ActorPick {
+  bool packed, dma;
+  hipFunction_t f;
+};
+template <typename real>
+int resolve_actor_instance(rcg_handle* h, const ActorPlan& L, bool streamed, ActorPick* p) {
+  p->packed = L.pack_ok && !(L.variant >= DMA_RQL_0 && !packed_critic_ok(h->dc, (int)sizeof(real)));
+  p->dma = !p->packed && L.dma_ok;
+  if (p->packed || p->dma) return dma_function<real>(h, p->packed, L.R, L.variant, &p->f);
+  return core_function<real>(h, expr_actor<real>(L.long_row || L.generic, L.tgt, streamed, L.long_row), &p->f);
+}
+
 // The decision step: the kernel launch_actor (rcg_sysops.hpp) picks for the same plan, except the instances written for one
 // built-in system (GenPk, k_ticks_pk).  The instance is resolved - and compiled, the first time - before anything is enqueued.
 template <typename real>
@@ -373,14 +475,12 @@ int actor(rcg_handle* h, const char* who, const void* cand, int K, const void* o
   }
   if (h->sub_hi > 0 && !(L.dma_ok && !L.pack_ok))
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: a split tick needs the k_actor_dma shape", who);
-  // (MPC only: the variants are DMA_MPC_G1 / DMA_MPC - the packed ones, diagonal stage cost - and DMA_MPC_GEND / GENF)
-  const bool packed = L.pack_ok, dma = !packed && L.dma_ok;
-  hipFunction_t f;
-  if (packed || dma)
-    rc = dma_function<real>(h, packed, L.R, L.variant, &f);
-  else
-    rc = core_function<real>(h, expr_actor<real>(L.long_row || L.generic, L.tgt, cand != nullptr, L.long_row), &f);
+  ActorPick pick;
+  rc = resolve_actor_instance<real>(h, L, cand != nullptr, &pick);
   if (rc) return rc;
+  const bool packed = pick.packed, dma = pick.dma;
+  hipFunction_t const f = pick.f;
+  // (a fused env step that was planned for a packed instance that does not exist runs as its own launch, first)
   const bool fuse_sim = packed && L.fuse_sim;
   if (sim_first && !fuse_sim) {
     rc = sim_step<real>(h, h->cfg.substeps_per_tick);
@@ -436,6 +536,7 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
     int rc = opt_plan<real>(h, h->du, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, wpb, lds);
     if (rc) return rc;
     KParams<real> P = params<real>(h);
+    // (RQL / SQL run on the generic instance, as they do for the built-in systems; its critic terms are over [y, u])
     const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
     const bool tgt = c.flags & RCG_FLAG_HAS_TARGET;
     const bool pairs = A.memory > 0;
@@ -457,9 +558,66 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
   });
 }
 
-int rtc_critic(rcg_handle* h, const void*, const void*, const void*, void*, int32_t) { return refuse(h, "rcg_critic"); }
-int rtc_critic_cost(rcg_handle* h, const void*, void*) { return refuse(h, "rcg_critic_cost"); }
-int rtc_critic_update(rcg_handle* h, int32_t, int32_t, int32_t) { return refuse(h, "the critic update"); }
+// ---- the critic entry points: op_critic, op_critic_cost and op_critic_update (rcg_sysops.hpp) on the critic program -----------
+int rtc_critic(rcg_handle* h, const void* obs, const void* act, const void* w, void* out, int32_t n) {
+  if (!h->rtc->dims.has_critic) return refuse(h, "rcg_critic");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), &f, nullptr, nullptr);
+    if (rc) return rc;
+    const real* o = (const real*)obs;
+    const real* a = (const real*)act;
+    const real* ww = (const real*)w;
+    real* y = (real*)out;
+    long nn = n;
+    KParams<real> P = params<real>(h);
+    void* args[] = {&o, &a, &ww, &y, &nn, &P};
+    return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+  });
+}
+
+int rtc_critic_cost(rcg_handle* h, const void* w, void* Jc) {
+  if (!h->rtc->dims.has_critic) return refuse(h, "rcg_critic_cost");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, &f, nullptr);
+    if (rc) return rc;
+    const real* ww = w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC];
+    const real* wp = (const real*)h->f[RCG_FIELD_W_PREV];
+    const real* ob = (const real*)h->f[RCG_FIELD_OBS_BUF];
+    const real* ab = (const real*)h->f[RCG_FIELD_ACT_BUF];
+    real* jc = (real*)Jc;
+    KParams<real> P = params<real>(h);
+    void* args[] = {&ww, &wp, &ob, &ab, &jc, &P};
+    return launch(h, f, dim3(blocks_for(h->cfg.batch)), dim3(256), 0, args);
+  });
+}
+
+int rtc_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t do_fit) {
+  if (!h->rtc->dims.has_critic) return refuse(h, "the critic update");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    // the form, the grid and the variant word of op_critic_update; the function is resolved before the scratch tensor of
+    // k_critic_fit_gen is sized and before anything is enqueued
+    hipFunction_t f;
+    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
+    if (rc) return rc;
+    ProfScope prof_scope(h, RCG_KERNEL_CRITIC);
+    FitArgs<real> F;
+    FitPlan L;
+    rc = fit_plan<real>(h, n_substeps, do_push, do_fit, false, F, L);
+    if (rc) return rc;
+    KParams<double> P64 = h->p64;
+    KParams<real> P = params<real>(h);
+    double* scratch = (double*)h->fit_scratch;
+    void* args[] = {&F, &P64, &P, &scratch};  // (the fourth is k_critic_fit_gen's alone)
+    rc = launch(h, f, L.grid, L.block, 0, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_CRITIC, RCG_KID_CRITIC_FIT, L.variant, L.epw);
+    return rc;
+  });
+}
 int rtc_nominal(rcg_handle* h, const void*, void*, void*, void*, int32_t, double, const double*, int32_t, bool) {
   return refuse(h, "the nominal controller");
 }
@@ -476,19 +634,19 @@ int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, i
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC> mangles its arguments as Lb0E / Lb1E and Li<n>E / Lin<n>E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT> mangles its arguments as Lb0E / Lb1E and Li<n>E / Lin<n>E)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
-                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v>";
+                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[5];
+  long v[6];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 5 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 6 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -499,7 +657,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 5) {
+  if (n != 6) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -508,6 +666,7 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.dy = (int)v[2];
   S.dims.has_out = v[3] != 0;
   S.dims.has_out_jac = S.dims.has_out && v[4] != 0;
+  S.dims.has_critic = v[5] != 0;
   return RCG_OK;
 }
 
@@ -532,6 +691,42 @@ int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
     KParams<real> P = params<real>(h);
     void* args[] = {&st, &y, &pe, &nn, &P};
     return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+  });
+}
+
+// rcg_control_tick, RQL / SQL: every instance the tick launches - the critic program's fit kernel and the decision kernel of this
+// (cand, K) - resolved, and compiled on first use, before the tick enqueues anything
+int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K) {
+  if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_tick");
+  int rc = by_dtype(h, [&](auto r) {
+    hipFunction_t f;
+    return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
+  });
+  if (rc) return rc;
+  return by_dtype(h, [&](auto r) {  // the tick's own plan (the arguments rcg_control_tick hands the launcher), and its instance
+    using real = decltype(r);
+    const RtcSystem& S = *h->rtc;
+    ActorArgs<real> A;
+    ActorPlan L;
+    int rc2 = actor_plan<real>(h, "rcg_control_tick", S.dims.ds, S.dims.du, S.tgt, cand, K, nullptr, nullptr, nullptr, nullptr,
+                               h->f[RCG_FIELD_ACTION], h->f[RCG_FIELD_BEST_J], (int32_t*)h->f[RCG_FIELD_BEST_IDX], true, false, A, L);
+    if (rc2) return rc2;
+    ActorPick pick;
+    return resolve_actor_instance<real>(h, L, cand != nullptr, &pick);
+  });
+}
+
+// rcg_control_tick_opt, RQL / SQL: the optimiser's own refusals and the critic program, before the critic phase enqueues anything
+// (the optimiser's instances belong to the core programs compiled at registration)
+int rtc_prepare_tick_opt(rcg_handle* h) {
+  const RtcDims& d = h->rtc->dims;
+  if (!d.has_critic) return refuse_critic(h, "rcg_control_tick_opt");
+  if (!d.has_jac || (d.has_out && !d.has_out_jac))
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_opt: the policy %s defines no jac_T%s (the optimiser's adjoint sweep)",
+                    h->rtc->name.c_str(), d.has_out ? " / out_jac_T" : "");
+  return by_dtype(h, [&](auto r) {
+    hipFunction_t f;
+    return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
   });
 }
 
@@ -577,7 +772,7 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   std::unique_ptr<RtcSystem> S(new RtcSystem);
   S->name = name;
   S->src = policy_src;
-  S->dims = RtcDims{ds, du, np, false, ds, false, false};
+  S->dims = RtcDims{ds, du, np, false, ds, false, false, false};
   S->tgt = false;
   std::string log;
   rc = probe(*S, &log);
@@ -591,11 +786,36 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
     rcg_set_thread_error(std::string("rcg_register_system: ") + name + ": " + log);
     return rc;
   }
+  for (const auto& e : core_exprs<float>(S->dims)) S->compiled.push_back(S->name + "_f32.hip\t" + e);
+  for (const auto& e : core_exprs<double>(S->dims)) S->compiled.push_back(S->name + "_f64.hip\t" + e);
   std::lock_guard<std::mutex> lock(g_mu);
   if (known(&rc)) return rc;
   S->id = RCG_SYS_USER_BASE + (int)g_sys.size();
   *sys_id = S->id;
   g_sys.push_back(std::move(S));
+  return RCG_OK;
+}
+
+int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic) {
+  RtcDims d{0, 0, 0, false, 0, false, false, true};  // (the built-in systems run every critic mode)
+  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_critic: bad sys_id %d", sys_id);
+  if (has_critic) *has_critic = d.has_critic ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need) {
+  std::lock_guard<std::mutex> lock(g_mu);
+  const int i = sys_id - RCG_SYS_USER_BASE;
+  if (i < 0 || i >= (int)g_sys.size()) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_programs: bad sys_id %d", sys_id);
+  std::string text;
+  for (const auto& line : g_sys[i]->compiled) text += line + "\n";
+  if (need) *need = (int64_t)text.size() + 1;
+  if (buf && cap > 0) {
+    const size_t n = text.size() < (size_t)cap - 1 ? text.size() : (size_t)cap - 1;
+    memcpy(buf, text.data(), n);
+    buf[n] = '\0';
+  }
   return RCG_OK;
 }
 

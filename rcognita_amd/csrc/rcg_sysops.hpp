@@ -211,90 +211,120 @@ static int fit_lanes_knob();  // (DevKnobs, below)
 // Round 6: from 9 weights (was 20) - the structures with 9-17 weights measured 1.2-1.3 x faster on four lanes in round 4 (2tank
 // quad-lin 83 -> 66 us, 3wrobotNI quad-mix 145 -> 116, 3wrobotNI quadratic 238 -> 196; 7 weights: 61 -> 59, 6 weights: 65 -> 89).
 constexpr int kFitLanesMinDc = 9;
-template <typename Sys, typename real, int CS>
-static bool launch_fit3(rcg_handle* h, const FitArgs<real>& F, bool force_ml) {
-  constexpr int DC = CriticDim<CS, Sys::DS, Sys::DU>::value;
+
+// The critic update's launch: which of the fit forms serves the handle, its grid and the word rcg_last_launch reports - decided
+// from runtime values alone (TD rows, the number of weights h->dc = dim_critic(structure, dim_output, dim_input), the envs of this
+// launch), before an instance is picked.  The built-in systems' launcher below and the runtime-compiled systems' one (rcg_rtc.hip)
+// both take it from fit_plan, as the decision launchers take theirs from actor_plan: a registered copy of a built-in system gets
+// the same kernel, form and grid.
+enum { FIT_FORM_3 = 0, FIT_FORM_3ML = 1, FIT_FORM_ROWS = 2, FIT_FORM_GEN = 3 };
+struct FitPlan {
+  int form;     // FIT_FORM_*: k_critic_fit<.., 3>, k_critic_fit_ml<.., 3>, k_critic_fit<.., kFitMaxRows>, k_critic_fit_gen
+  dim3 grid, block;
+  int variant;  // rcg_last_launch's variant word
+  int epw;      // ... and envs per wave
+};
+static inline int fit_form_of(int m, int dc, bool force_ml) {
+  if (m > kFitMaxRows) return FIT_FORM_GEN;
+  if (m > 3) return FIT_FORM_ROWS;
+  return (dc >= kFitLanesMinDc || force_ml) ? FIT_FORM_3ML : FIT_FORM_3;
+}
+// Fills the kernel arguments and the plan, and sizes the scratch tensor of k_critic_fit_gen; returns RCG_OK or the error of a
+// failed allocation (nothing launched).
+template <typename real>
+static int fit_plan(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t do_fit, bool force_ml, FitArgs<real>& F, FitPlan& L) {
+  const int m = h->cfg.n_critic - 1;
+  memset(&F, 0, sizeof F);
+  F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
+  F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
+  F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
+  F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
+  F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
+  F.do_sim = n_substeps > 0;
+  F.do_push = do_push;
+  F.do_fit = do_fit;
+  F.state = (const real*)h->f[RCG_FIELD_STATE];
+  F.action = (const real*)h->f[RCG_FIELD_ACTION];
+  F.sim.state = (real*)h->f[RCG_FIELD_STATE];
+  F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
+  F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  F.sim.n_sub = n_substeps;
+  F.env_lo = h->sub_lo;  // (a half of a split tick; 0, 0: the whole batch)
+  F.env_hi = h->sub_hi;
   const long n_env = h->sub_hi > 0 ? h->sub_hi - h->sub_lo : h->cfg.batch;
-  const dim3 block(64), grid(blocks_for(n_env, 64)), grid_ml(blocks_for(n_env, 64 / FIT_L));
+  L.form = fit_form_of(m, h->dc, force_ml);
+  const bool gen = L.form == FIT_FORM_GEN, fit_ml = L.form == FIT_FORM_3ML;
+  L.block = dim3(64);
+  L.grid = dim3(blocks_for(n_env, fit_ml ? 64 / FIT_L : 64));
+  L.variant = h->cfg.critic_struct + 16 * (m <= 3 ? 3 : (gen ? 0 : kFitMaxRows)) + (F.do_sim ? 256 : 0) + (do_fit ? 512 : 0) +
+              (fit_ml ? 1024 : 0) + (gen ? 2048 : 0);
+  L.epw = fit_ml ? 16 : 64;
+  // more TD rows than the register kernels hold (Ncritic - 1 > 8; the reference only clips Ncritic to buffer_size - 1,
+  // controllers.py:1015): k_critic_fit_gen with the env's stack and factor in a scratch tensor of the handle, allocated on
+  // first use (rcg_critic_fit_gen.hpp)
+  if (gen && do_fit) {
+    const size_t need = (size_t)fit_gen_scratch_doubles(m, h->dc) * (size_t)h->cfg.batch * sizeof(double);
+    if (h->fit_scratch_bytes < need) {
+      if (h->fit_scratch) {
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        HIPCHK(h, hipFree(h->fit_scratch));
+        h->fit_scratch = nullptr;
+        h->fit_scratch_bytes = 0;
+      }
+      if (hipMalloc(&h->fit_scratch, need) != hipSuccess) {
+        (void)hipGetLastError();
+        return rcg_fail(h, RCG_ERR_HIP, "critic fit with %d TD rows: cannot allocate %zu bytes of scratch for %d envs", m, need,
+                        h->cfg.batch);
+      }
+      h->fit_scratch_bytes = need;
+    }
+  }
+  return RCG_OK;
+}
+
+// (a structure with kFitLanesMinDc weights or more has the four-lane instance only; the others have the one-lane one, and the
+// four-lane one in the dev build, where RCG_FIT_LANES=4 forces it)
+template <typename Sys, typename real, int CS>
+static void launch_fit3(rcg_handle* h, const FitArgs<real>& F, const FitPlan& L) {
+  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
   if constexpr (DC >= kFitLanesMinDc) {
-    RCG_LAUNCH(h, (k_critic_fit_ml<Sys, real, CS, 3>), grid_ml, block, 0, F, h->p64, params<real>(h));
-    return true;
+    RCG_LAUNCH(h, (k_critic_fit_ml<Sys, real, CS, 3>), L.grid, L.block, 0, F, h->p64, params<real>(h));
   } else {
 #ifdef RCG_DEV
-    if (force_ml) {
-      RCG_LAUNCH(h, (k_critic_fit_ml<Sys, real, CS, 3>), grid_ml, block, 0, F, h->p64, params<real>(h));
-      return true;
+    if (L.form == FIT_FORM_3ML) {
+      RCG_LAUNCH(h, (k_critic_fit_ml<Sys, real, CS, 3>), L.grid, L.block, 0, F, h->p64, params<real>(h));
+      return;
     }
 #endif
-    RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS, 3>), grid, block, 0, F, h->p64, params<real>(h));
-    return false;
+    RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS, 3>), L.grid, L.block, 0, F, h->p64, params<real>(h));
   }
 }
 
 template <typename Sys>
 int op_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t do_fit) {
-  const int m = h->cfg.n_critic - 1;
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     ProfScope prof_scope(h, RCG_KERNEL_CRITIC);
     FitArgs<real> F;
-    memset(&F, 0, sizeof F);
-    F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
-    F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
-    F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
-    F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
-    F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
-    F.do_sim = n_substeps > 0;
-    F.do_push = do_push;
-    F.do_fit = do_fit;
-    F.state = (const real*)h->f[RCG_FIELD_STATE];
-    F.action = (const real*)h->f[RCG_FIELD_ACTION];
-    F.sim.state = (real*)h->f[RCG_FIELD_STATE];
-    F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-    F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
-    F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
-    F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-    F.sim.n_sub = n_substeps;
-    F.env_lo = h->sub_lo;  // (a half of a split tick; 0, 0: the whole batch)
-    F.env_hi = h->sub_hi;
-    const dim3 grid(blocks_for(h->sub_hi > 0 ? h->sub_hi - h->sub_lo : h->cfg.batch, 64)), block(64);
-    bool fit_ml = false;
+    FitPlan L;
 #ifdef RCG_DEV
     const bool force_ml = fit_lanes_knob() == FIT_L;  // RCG_FIT_LANES=4: the four-lane form for every structure (experiments)
 #else
     const bool force_ml = false;
 #endif
-    // more TD rows than the register kernels hold (Ncritic - 1 > 8; the reference only clips Ncritic to buffer_size - 1,
-    // controllers.py:1015): k_critic_fit_gen with the env's stack and factor in a scratch tensor of the handle, allocated on
-    // first use (rcg_critic_fit_gen.hpp)
-    const bool gen = m > kFitMaxRows;
-    if (gen && do_fit) {
-      const size_t need = (size_t)fit_gen_scratch_doubles(m, h->dc) * (size_t)h->cfg.batch * sizeof(double);
-      if (h->fit_scratch_bytes < need) {
-        if (h->fit_scratch) {
-          HIPCHK(h, hipStreamSynchronize(h->stream));
-          HIPCHK(h, hipFree(h->fit_scratch));
-          h->fit_scratch = nullptr;
-          h->fit_scratch_bytes = 0;
-        }
-        if (hipMalloc(&h->fit_scratch, need) != hipSuccess) {
-          (void)hipGetLastError();
-          return rcg_fail(h, RCG_ERR_HIP, "critic fit with %d TD rows: cannot allocate %zu bytes of scratch for %d envs", m, need,
-                          h->cfg.batch);
-        }
-        h->fit_scratch_bytes = need;
-      }
-    }
+    const int rc = fit_plan<real>(h, n_substeps, do_push, do_fit, force_ml, F, L);
+    if (rc) return rc;
 #define RCG_FIT(CS)                                                                                                    \
   do {                                                                                                                 \
-    if (m <= 3)                                                                                                        \
-      fit_ml = launch_fit3<Sys, real, CS>(h, F, force_ml);                                                             \
-    else if (!gen)                                                                                                     \
-      RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS, kFitMaxRows>), grid, block, 0, F, h->p64,             \
-                         params<real>(h));                                                                             \
+    if (L.form == FIT_FORM_3 || L.form == FIT_FORM_3ML)                                                                \
+      launch_fit3<Sys, real, CS>(h, F, L);                                                                             \
+    else if (L.form == FIT_FORM_ROWS)                                                                                  \
+      RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS, kFitMaxRows>), L.grid, L.block, 0, F, h->p64, params<real>(h));       \
     else                                                                                                               \
-      RCG_LAUNCH(h, (k_critic_fit_gen<Sys, real, CS>), grid, block, 0, F, h->p64, params<real>(h),                     \
+      RCG_LAUNCH(h, (k_critic_fit_gen<Sys, real, CS>), L.grid, L.block, 0, F, h->p64, params<real>(h),                 \
                  (double*)h->fit_scratch);                                                                             \
   } while (0)
     switch (h->cfg.critic_struct) {
@@ -304,10 +334,7 @@ int op_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t
       default: RCG_FIT(RCG_CRITIC_QUAD_MIX); break;
     }
 #undef RCG_FIT
-    note_launch(h, RCG_KERNEL_CRITIC, RCG_KID_CRITIC_FIT,
-                h->cfg.critic_struct + 16 * (m <= 3 ? 3 : (gen ? 0 : kFitMaxRows)) + (F.do_sim ? 256 : 0) + (do_fit ? 512 : 0) +
-                    (fit_ml ? 1024 : 0) + (gen ? 2048 : 0),
-                fit_ml ? 16 : 64);
+    note_launch(h, RCG_KERNEL_CRITIC, RCG_KID_CRITIC_FIT, L.variant, L.epw);
     HIPCHK(h, hipGetLastError());
     return (int)RCG_OK;
   });
@@ -513,7 +540,7 @@ static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_t
   else
     variant = DMA_SQL_0 + c.critic_struct;
   L.variant = variant;
-  const size_t wslot = (size_t)4 * dma_wslot((int)esz, variant, DS, DU);  // critic weights parked in LDS (> 9 of them)
+  const size_t wslot = (size_t)4 * dma_wslot((int)esz, variant, h->dy, DU);  // critic weights parked in LDS (> 9 of them)
   // (an env's rows must be a whole number of 16-byte pieces, K * R * esz % 16 == 0 - any K for rows of 16 n bytes such as C2's
   // 80, every 4th K for the shortest rows: then every env starts 16-B aligned and a ragged last tile ends on a piece)
   const bool slab16 = ((size_t)K * row_bytes) % 16 == 0;
@@ -579,7 +606,7 @@ static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_t
     // SQL quad-lin 307 -> 280 us, SQL quadratic 261 -> 232); MPC and the small structures lose 1-2 % with 4
     const bool valu_heavy = variant == DMA_MPC_GENF ||  // (35-77 fused multiply-adds per step of stage cost)
                             variant >= DMA_RQL_GEN_0 ||
-                            ((dma_is_rql(variant) || dma_is_sql(variant)) && (size_t)dma_dc(dma_cs(variant), DS, DU) * esz >= 68);
+                            ((dma_is_rql(variant) || dma_is_sql(variant)) && (size_t)dma_dc(dma_cs(variant), h->dy, DU) * esz >= 68);
     const int per_cu = knobs.per_cu > 0 ? knobs.per_cu : ((row_bytes >= 20 * esz && long_slab && !valu_heavy) ? 2 : 4);
     // J staging (operator mode): all envs of the wave when that fits under 64 KB next to the tiles, else env by env
     const int jwave = (A.J && 4 * tile + wslot + 4 * esz * gpw * K <= (size_t)64 * 1024) ? 1 : 0;
@@ -1097,7 +1124,7 @@ int op_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
   const rcg_cfg& c = h->cfg;
   if (!ticks_mem_ok<Sys>(h)) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: no persistent RQL/SQL instance for this observation target");
   // (structures with >= 20 weights fit with four lanes per env: the wave's envs must fit its 16 quads)
-  if (dma_dc(c.critic_struct, Sys::DS, Sys::DU) >= kFitLanesMinDc && c.n_critic - 1 <= 3 && K < 4)
+  if (dma_dc(c.critic_struct, sys_dy<Sys>(), Sys::DU) >= kFitLanesMinDc && c.n_critic - 1 <= 3 && K < 4)
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: K >= 4 with this critic structure (four lanes per env in the fit)");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
@@ -1160,7 +1187,7 @@ int op_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
 #define RCG_TM(CS)                                                                                              \
   do {                                                                                                          \
-    constexpr bool ml_ = CriticDim<CS, Sys::DS, Sys::DU>::value >= kFitLanesMinDc;                              \
+    constexpr bool ml_ = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value >= kFitLanesMinDc;                          \
     if (m <= 3 && cand)                                                                                         \
       RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS, 3, Sys::TGT, ml_, true>), grid, block, lds, M, h->p64, P);      \
     else if (m <= 3)                                                                                            \

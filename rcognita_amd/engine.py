@@ -793,6 +793,10 @@ class Engine:
     def critic_update(self, do_fit=True):
         N.check(N.lib().rcg_critic_update(self._h, 1 if do_fit else 0), self._h)
 
+    def critic_fit(self):
+        """The fit alone, on the handle's buffers as they are - no push (rcg_critic_fit)."""
+        N.check(N.lib().rcg_critic_fit(self._h), self._h)
+
     def episode_reset(self):
         N.check(N.lib().rcg_episode_reset(self._h), self._h)
 

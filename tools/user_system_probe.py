@@ -7,6 +7,9 @@ times the streamed f64 tick at 65 536 envs x 256 candidates x Nactor 10 from the
 pendulum, on the small-angle pendulum (no trigonometry) and on Sys2Tank (same DS / DU, same kernel shape), as a fraction of
 8 TB/s of candidate bytes.  The same for the pendulum with an output map y = (sin th, cos th, om) (DY = 3, out, out_jac_T;
 DESIGN.md §13.1): its registration, its first streamed tick and its streamed f64 tick next to the pendulum without one.
+RQL (policies with CRITIC): the first-use compile time of a critic program and of a DMA_RQL_* instance; the
+streamed f64 RQL tick of a Sys2Tank copy interleaved with the built-in Sys2Tank (the same code shape: any gap beyond the
+run-to-run spread is a finding); the same tick of the pendulum with the output map.
 GPU box only; no torch.
 
     python tools/user_system_probe.py [B] [K] [Nactor]
@@ -130,3 +133,69 @@ for name, sid, pars, R1 in (("pendulum (runtime)", info["sys_id"], [1.3, 9.81, 0
 for name, ll, t, frac in rows:
     print(f"{name:22s} {ll['kernel']} variant {ll['variant']} gpw {ll['envs_per_wave']}: decision {t * 1e6:.1f} us, "
           f"{frac:.3f} of 8 TB/s")
+
+
+# ---- RQL on policies with CRITIC -----------------------------------------------------------------------------
+def with_critic(src, extra=""):
+    i = src.index("static constexpr int DS")
+    j = src.index("\n", i) + 1
+    return src[:j] + "  static constexpr bool CRITIC = true;\n" + extra + src[j:]
+
+
+def tank_copy(name):
+    src = open(os.path.join(ROOT, "rcognita_amd", "csrc", "rcg_systems.hpp")).read()
+    i = src.index("struct Sys2Tank {")
+    return with_critic(src[i:src.index("\n};\n", i) + 4].replace("struct Sys2Tank {", f"struct {name} {{"))
+
+
+tank = N.register_system("TankCriticProbe", tank_copy("TankCriticProbe"), 2, 1, 5)
+outc = N.register_system("PendulumOutCriticProbe", with_critic(PENDULUM_OUT.replace("PendulumT", "PendulumOutCriticProbe"),
+                                                                "  static constexpr bool TGT = true;\n"), 2, 1, 3)
+assert tank["has_critic"] and outc["has_critic"]
+TANK_PARS, TANK_R1, TANK_TGT, TANK_BND = [18.4, 24.4, 1.3, 1.0, 0.2], np.diag([10.0, 10.0, 1.0]), [0.5, 0.5], np.array([[0.0, 1.0]])
+
+
+def rql_engine(sid, pars, R1, target, bnds, dt):
+    e = Engine(EngineConfig(sys_id=sid, batch=B, dtype="f64", Nactor=NH, mode="RQL", critic_struct="quad-nomix", Ncritic=4,
+                            buffer_size=10, gamma=0.95, pars=pars, ctrl_bnds=bnds, R1=R1, observation_target=target, dt_sim=dt,
+                            sampling_time=dt, pred_step_size=2 * dt))
+    e.set_tick_parts(1)  # the built-in handle would split a tick of this size on a stream of its own: like for like
+    return e
+
+
+engines = []
+for name, sid, pars, R1, tgt, bnds, lo, hi in (
+        ("Sys2Tank copy (runtime)", tank["sys_id"], TANK_PARS, TANK_R1, TANK_TGT, TANK_BND, 0.0, 1.0),
+        ("Sys2Tank (built-in)", N.SYS_2TANK, TANK_PARS, TANK_R1, TANK_TGT, TANK_BND, 0.0, 1.0),
+        ("pendulum with out (runtime)", outc["sys_id"], [1.3, 9.81, 0.7], R1_OUT, [0.0, 1.0, 0.0], np.array([[-5.0, 5.0]]), -5.0, 5.0)):
+    e = rql_engine(sid, pars, R1, tgt, bnds, 0.1 if len(pars) == 5 else 0.01)
+    e.set_state(rng.uniform(0, 1, (B, 2)))
+    cand = e.to_device(rng.uniform(lo, hi, (B, K, NH, 1)))
+    t0 = time.perf_counter()
+    e.critic_cost()
+    e.synchronize()
+    t1 = time.perf_counter()
+    e.control_tick(cand)
+    e.synchronize()
+    t2 = time.perf_counter()
+    ll = e.last_launch()
+    print(f"{name}: first rcg_critic_cost (compiles the critic program: k_critic, k_critic_cost, k_critic_fit) {t1 - t0:.2f} s; "
+          f"first RQL tick (compiles {ll['kernel']} variant {ll['variant']} at R = {NH}) {t2 - t1:.2f} s")
+    for _ in range(5):
+        e.control_tick(cand)
+    e.synchronize()
+    e.profile([N.KERNEL_ACTOR, N.KERNEL_CRITIC])
+    engines.append((name, e, cand))
+for _ in range(5):  # interleaved: ten ticks of each handle in turn
+    for name, e, cand in engines:
+        for _ in range(10):
+            e.control_tick(cand)
+        e.synchronize()
+for name, e, cand in engines:
+    ta, tc = e.profile_samples(N.KERNEL_ACTOR) * 1e-3, e.profile_samples(N.KERNEL_CRITIC) * 1e-3
+    la, lc = e.last_launch(), e.last_launch(N.KERNEL_CRITIC)
+    blocks = np.median(ta.reshape(5, -1), axis=1) * 1e6
+    print(f"{name:28s} {la['kernel']} variant {la['variant']} gpw {la['envs_per_wave']}: decision {np.median(ta) * 1e6:.1f} us "
+          f"({B * K * NH * 8 / np.median(ta) / PEAK:.3f} of 8 TB/s; medians of the five blocks {blocks.min():.1f} .. {blocks.max():.1f}), "
+          f"{lc['kernel']} variant {lc['variant']}: env step + push + fit {np.median(tc) * 1e6:.1f} us")
+    e.close()
