@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 122 /* 121 + RQL / SQL on registered systems (policy member CRITIC): rcg_system_has_critic, rcg_system_programs, rcg_critic_fit */
+#define RCG_VERSION 123 /* 122 + rcg_last_launch_zero_w (the zero-weight instance of the float64 streamed decision) */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -344,7 +344,11 @@ int rcg_loop_step_end(rcg_handle* h, double* out);
  * ZERO weight makes J NaN (0 * inf) and the candidate counts as +inf, exactly as in the reference.  The generated grid with
  * the presets' R1 does not accumulate its zero-weighted terms (v, omega, F, M of the robots) step by step; it tests the
  * zero-weighted state components once, on the observation and on the last rolled-out state (a non-finite value is sticky
- * under the Euler step), with the same outcome (tests/test_hip_reset_and_guards.py). */
+ * under the Euler step), with the same outcome (tests/test_hip_reset_and_guards.py).  The float64 streamed decision of such
+ * a handle (k_actor_dma, gamma = 1, no J output; rcg_last_launch_zero_w) follows the same rule: it tests the observation, the
+ * last rolled-out state and the last action.  One difference to the full sum remains in both: a FINITE zero-weighted
+ * component whose square overflows (|.| >= 1.3e154) somewhere in the middle of the horizon, and nowhere in the three places
+ * tested, no longer turns J into NaN.  rcg_actor_cost writes the full sum. */
 int rcg_actor_argmin(rcg_handle* h, const void* cand, int32_t K, const void* obs, const void* state_sys,
                      void* action, void* best_J, int32_t* best_idx);
 /* One env.control-step for every env (the loop body of presets/main_3wrobot.py:419-429):
@@ -542,6 +546,11 @@ typedef enum rcg_kernel_id {
  * packs into one 64-row tile (k_actor, k_ticks); 64 for lane = env kernels.  Bit 12 (4096) of variant: the launch served one half
  * of a split tick (rcg_set_tick_parts).  Each out pointer may be NULL. */
 int rcg_last_launch(const rcg_handle* h, int32_t kind, int32_t* kernel_id, int32_t* variant, int32_t* envs_per_wave);
+/* The components of chi = [y - target, u] whose cost terms the instance of the last launch of `kind` did not accumulate,
+ * because their stage weights are exactly zero (bit i: chi_i): the system's preset mask on k_actor_dma's zero-weight instance
+ * (0x78 on the 3-wheel robot, 0x18 on the kinematic one: float64, MPC, gamma = 1, the preset's zero weights, no J output),
+ * 0 for every other launch.  Kernel and variant are reported by rcg_last_launch as for the plain instance. */
+int rcg_last_launch_zero_w(const rcg_handle* h, int32_t kind, uint32_t* mask);
 /* "k_actor_dma", ... ; "?" for an unknown id.  Never NULL. */
 const char* rcg_kernel_name(int32_t kernel_id);
 

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librcg.so")
 
 # ---- enums (include/rcg.h) -------------------------------------------------------------------
-RCG_VERSION = 122
+RCG_VERSION = 123
 OK, ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_NONFINITE = 0, -1, -2, -3, -4, -5
 SYS_3WROBOT, SYS_3WROBOT_NI, SYS_2TANK = 0, 1, 2
 MODE_MPC, MODE_RQL, MODE_SQL = 0, 1, 2
@@ -54,7 +54,7 @@ SYMBOLS = [
     "rcg_profile_samples", "rcg_last_launch", "rcg_kernel_name", "rcg_wait_stream", "rcg_nominal_theta", "rcg_set_optimizer", "rcg_set_optimizer_tol", "rcg_set_tick_parts", "rcg_join", "rcg_loop_step", "rcg_loop_step_begin", "rcg_loop_step_end",
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
-    "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit",
+    "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit", "rcg_last_launch_zero_w",
 ]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
@@ -179,6 +179,7 @@ def lib():
         "rcg_profile_read": (C.c_int, [vp, i32, C.POINTER(C.c_double), C.POINTER(i64)]),
         "rcg_profile_samples": (C.c_int, [vp, i32, C.POINTER(C.c_double), i64, C.POINTER(i64)]),
         "rcg_last_launch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32)]),
+        "rcg_last_launch_zero_w": (C.c_int, [vp, i32, C.POINTER(C.c_uint32)]),
         "rcg_kernel_name": (C.c_char_p, [i32]),
         "rcg_wait_stream": (C.c_int, [vp, vp]),
         "rcg_release_stream": (C.c_int, [vp, vp]),

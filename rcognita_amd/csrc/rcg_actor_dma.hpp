@@ -36,10 +36,24 @@
 //        (v_readfirstlane): 2 of the 9 sincos of a Nactor = 10 rollout and 7 accumulations go, 491 -> 417 instructions
 //        per tile in f64, for ~140 per env (T = 4 tiles), at 161 VGPRs (159 before); measured: DESIGN.md 6.  Horizons of
 //        1 and 2 steps take the part of the prefix they have;
+//        Zero-weight instance (template parameter ZW = the policy's ZW_PRESET; float64, DMA_MPC_G1, no output map - the
+//        headline: the 3-wheel robot's R1 = diag[1, 10, 1, 0, 0, 0, 0]): a component whose stage weight is exactly zero has
+//        no sum S_i - no fma per step, no fma(0, S_i, J) at the end, no shared term in the prefix.  fma(0, S_i, J) is J bit
+//        for bit for a finite S_i and NaN otherwise, so the instance tests the skipped components where a non-finite value
+//        cannot hide: y_0 (once per env, in scalar registers), the last rolled-out state (every earlier action has entered
+//        it and NaN / inf is sticky under x += h f) and the last action (it enters nothing) - the rule of rollout_cost's ZW
+//        (rcg_kernels.hpp).  4 of the 36 float64 operations of a step go, 161 -> 153 VGPRs; rcg_dma_launch.hpp takes the
+//        instance when the handle's zero weights cover the preset's and the launch has no J output (dma_zero_w below);
+//        the variant word stays DMA_MPC_G1, rcg_last_launch_zero_w reports the mask.  f32 hides its rollout behind the
+//        stream and keeps the one instance; measured: DESIGN.md 6;
 // The only vmcnt wait is the one in front of step 2 of the NEXT tile, which is exactly the data it needs.
 // vmcnt retires in issue order, so whatever else the next iteration needs from memory (the next env's state)
 // is requested BEFORE the tile loads and never drains them.
-//     5. per env: wave argmin (f32: packed (cost, index) key, DPP + v_readlane, rcg_math.hpp; f64: shuffle butterfly);
+//     5. per env: wave argmin (f32: packed (cost, index) key, DPP + v_readlane, rcg_math.hpp; f64: the __shfl_xor butterfly -
+//        18 ds_bpermute in six dependent LDS round trips at the end of an env's last tile, the longest compute phase of the
+//        wave - except in the zero-weight instance, which minimises the cost and then the index among the lanes that hold
+//        the minimum with the same DPP stages and v_readlane, no LDS: wave_argmin_reg; the other float64 instances keep
+//        the butterfly and with it their registers and occupancy, profiles/r09_dma_resources.txt);
 //        the winner is parked in lane (env - env0).  When the wave's envs are done, lanes < n_envs store action / best_J
 //        / best_idx coalesced and issue ACCUM / STEP_IDX as no-return atomics (one adder per address: still
 //        deterministic).  Per-env 4-byte writes from lane 0 cost 7 % (scattered partial-line writes interleaved with the
@@ -53,8 +67,12 @@
 // measurements: 1 rollout, 2 argmin + writes, 4 env-state loads.  The production library compiles them out.
 // Tried and removed: two tiles in flight per wave (1.5-3 % slower), the tick's env step fused into the
 // prologue (a wash: +3-4 % kernel time against one saved 7-us launch).
-// s_setprio around landing -> re-issue (RCG_DMA_PRIO, off): no effect on the f32 kernel in round 2; the float64 A/B of this
-// change is recorded in DESIGN.md 6.  The tank's and the kinematic robot's prefix hooks (registers: rcg_systems.hpp).
+// s_setprio around landing -> re-issue (RCG_DMA_PRIO, off): no effect on the f32 kernel in round 2; the float64 A/B of the
+// lean hand-over is recorded in DESIGN.md 6.  The tank's and the kinematic robot's prefix hooks (registers: rcg_systems.hpp).
+// The register argmin in every float64 instance: 970 instances move by a few registers, 21 of them across an occupancy step
+// (profiles/r09_dma_resources.txt) - kept to the instance whose launches are measured.
+// A/B switches of the zero-weight instance (`make ab ABFLAGS=...`): -DRCG_AB_NO_DMA_ZW (every launch on the plain instance),
+// -DRCG_AB_SHFL_ARGMIN64 (the butterfly in the zero-weight instance too).
 #pragma once
 #include <hip/hip_ext.h>
 #include "rcg_kernels.hpp"
@@ -146,6 +164,32 @@ __device__ __forceinline__ void wave_argmin(double& bestJ, int& bestI) {
     }
   }
 }
+// k_actor_dma's zero-weight instance: the float64 pair without LDS round trips (rcg_math.hpp) - the minimum cost over the
+// wave, then the lowest index among the lanes that hold it (a lane without a row holds +inf and 0x7fffffff: it never wins).
+// The cost is never NaN here.  The butterfly above stays for every other instance and kernel (and for
+// `make ab ABFLAGS=-DRCG_AB_SHFL_ARGMIN64`).
+__device__ __forceinline__ void wave_argmin_reg(float& bestJ, int& bestI) { wave_argmin(bestJ, bestI); }
+__device__ __forceinline__ void wave_argmin_reg(double& bestJ, int& bestI) {
+#ifdef RCG_AB_SHFL_ARGMIN64
+  wave_argmin(bestJ, bestI);
+#else
+  const double Jmin = wave_min_f64(bestJ);
+  bestI = (int)wave_min_u32(bestJ == Jmin ? (unsigned)bestI : 0x7fffffffu);
+  bestJ = Jmin;
+#endif
+}
+
+// The zero-weight specialisation of the DMA_MPC_G1 instance (template parameter ZW of k_actor_dma): float64 only - the f32
+// kernel hides its rollout behind the stream, the float64 one does not - and policies without an output map.
+// ZW is 0 or the policy's ZW_PRESET; a handle takes the instance when its own zero weights cover the preset's and the launch
+// has no J output (operator mode keeps the plain instance: J's bits are an output there).
+template <typename Sys, typename real>
+__host__ __device__ constexpr unsigned dma_zw_preset() {
+  if constexpr (sizeof(real) == 8 && !HasOut<Sys>::value)
+    return Sys::ZW_PRESET;
+  else
+    return 0u;
+}
 
 // A policy with the optional prefix hook (rcg_systems.hpp: PFX_FREE, PFX_HEADING, rhs_trig); one without it compiles to the
 // plain rollout
@@ -210,7 +254,7 @@ __device__ __forceinline__ void dma_pieces(const unsigned char* g, unsigned off,
 // rows of 40 and 48 bytes (Nactor = 5, 6) gained nothing and stay at one row per lane.
 __host__ __device__ constexpr int dma_rpl(int r, int esz) { return r * esz <= 24 ? 4 : (r * esz <= 32 ? 2 : 1); }
 
-template <typename Sys, typename real, int R, bool TGT, int V>
+template <typename Sys, typename real, int R, bool TGT, int V, unsigned ZW = 0u>
 __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, const KParams<real> P) {
   constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, NP = Sys::NP;
   constexpr bool OUT = HasOut<Sys>::value;  // an output map (registered systems only); else y = x
@@ -218,6 +262,9 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   constexpr bool GEND = V == DMA_MPC_GEND, GENF = V == DMA_MPC_GENF, GEN = GEND || GENF;
   constexpr bool GENR = V >= DMA_RQL_GEN_0;  // RQL whose stage cost is not the presets' diagonal quadratic one: stage_any per step
   static_assert(!(GEN || GENR) || TGT, "the generic-cost instances subtract a target (zeros for a handle without one)");
+  // ZW: bit i set - chi_i has stage weight exactly zero in every handle this instance serves: its sum S_i does not exist
+  static_assert(ZW == 0u || (G1 && sizeof(real) == 8 && !OUT && ZW == Sys::ZW_PRESET),
+                "the zero-weight instance: DMA_MPC_G1, float64, no output map, the policy's preset mask");
   constexpr int CS = dma_cs(V);  // compile-time critic structure
   constexpr int DCMAX = CRIT ? dma_dc(CS, DY, DU) : 1;
   constexpr int ESZ = (int)sizeof(real);
@@ -410,6 +457,7 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
   // what the candidates of env b share (PFX; wave-uniform, in scalar registers): the action-free components of x_1, the
   // trig of alpha_1, and the cost terms of y_0 (and of those components of y_1) as the rollout would have summed them
   real x1s[DS], trig0[2] = {0, 0}, trig1[2] = {0, 0}, Sini[DY];
+  real zw0 = 0;  // (ZW) the zero-weighted components of y_0: 0, or NaN if one of them is not finite
 #pragma unroll
   for (int c = 0; c < DS; ++c) x1s[c] = 0;
 #pragma unroll
@@ -487,6 +535,7 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
       if constexpr (G1) {
 #pragma unroll
         for (int c = 0; c < DY; ++c) {
+          if ((ZW >> c) & 1u) continue;
           const real chi0 = TGT ? y0[c] - P.target[c] : y0[c];
           real a = fma_r(chi0, chi0, (real)0);
           if (N >= 2 && ((FREE >> c) & 1u)) {
@@ -496,6 +545,13 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
           Sini[c] = uniform_r(a);
         }
       }
+    }
+    if constexpr (ZW != 0u) {  // as rollout_cost has it (rcg_kernels.hpp): once per env, wave-uniform
+      real z = 0;
+#pragma unroll
+      for (int i = 0; i < DY; ++i)
+        if ((ZW >> i) & 1u) z = fma_r(P.R1d[i], y0[i] * y0[i], z);
+      zw0 = uniform_r(z);
     }
     bestJ = inf_r<real>();
     bestI = 0x7fffffff;
@@ -604,6 +660,7 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
             for (int i = 0; i < NCHI; ++i) {
               // (PFX: S starts from the env's terms of y_0 and of the action-free components of y_1)
               if (PFX && i < DY && (kk == 0 || (kk == 1 && ((FREE >> i) & 1u)))) continue;
+              if ((ZW >> i) & 1u) continue;  // weight exactly zero: fma(0, S_i, J) == J for a finite S_i
               S[i] = fma_r(chi[i], chi[i], S[i]);
             }
           } else if (SQL) {
@@ -620,7 +677,21 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
         }
         if (G1) {
 #pragma unroll
-          for (int i = 0; i < NCHI; ++i) J = fma_r(P.R1d[i], S[i], J);
+          for (int i = 0; i < NCHI; ++i)
+            if (!((ZW >> i) & 1u)) J = fma_r(P.R1d[i], S[i], J);
+          // ... and NaN for a non-finite S_i (0 * inf), which is what numpy's chi R1 chi gives the reference.  The skipped
+          // components are tested once: on y_0 (zw0), on the last rolled-out state - every earlier action has entered it, and
+          // inf / NaN is sticky under x += h f - and on the last action, which enters nothing.  All of these are exact zeros
+          // for finite inputs: J keeps its bits
+          if constexpr (ZW != 0u) {
+#pragma unroll
+            for (int i = 0; i < DY; ++i)
+              if ((ZW >> i) & 1u) J = fma_r(P.R1d[i], y[i] * y[i], J);
+#pragma unroll
+            for (int c = 0; c < DU; ++c)
+              if ((ZW >> (DY + c)) & 1u) J = fma_r(P.R1d[DY + c], cur[(N - 1) * DU + c] * cur[(N - 1) * DU + c], J);
+            J += zw0;
+          }
         }
         if (SQL) {  // J = w . sum_k phi(chi_k)
 #pragma unroll
@@ -666,7 +737,10 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
       }
       // the winner's first action is read from the winner's lane: every lane kept the action of its own best row,
       // and bestI = tile * 64 + lane
-      wave_argmin(bestJ, bestI);
+      if constexpr (ZW != 0u)
+        wave_argmin_reg(bestJ, bestI);
+      else
+        wave_argmin(bestJ, bestI);
       const int wl = __builtin_amdgcn_readfirstlane(bestI & 63);
 #pragma unroll
       for (int c = 0; c < DU; ++c) bu[c] = readlane_r(bu[c], wl);
@@ -712,6 +786,17 @@ __global__ __launch_bounds__(256) void k_actor_dma(const ActorArgs<real> A, cons
 // Returns false when there is no instance for (row length r, variant).  ev_a / ev_b (both or neither): the launch carries
 // them as its start / stop events (rcg_profile, rcg_handle.hpp::ProfScope).
 #if !defined(__HIPCC_RTC__)  // (host code: not part of a runtime-compiled program, rcg_rtc.hip)
+// The mask of the zero-weight instance that serves this launch, 0: the plain instance (`preset`: dma_zw_preset of the policy).
+// One rule for launch_dma, which picks the instance, for launch_actor, which records it (rcg_last_launch_zero_w), and for the
+// systems compiled at run time.  `make ab ABFLAGS=-DRCG_AB_NO_DMA_ZW` keeps every launch on the plain instance.
+template <typename real>
+static inline unsigned dma_zero_w(unsigned preset, int variant, const ActorArgs<real>& A, const KParams<real>& P) {
+#ifdef RCG_AB_NO_DMA_ZW
+  return 0u;
+#else
+  return (preset != 0u && variant == DMA_MPC_G1 && !A.J && (P.zero_w & preset) == preset) ? preset : 0u;
+#endif
+}
 template <typename Sys, typename real, int GROUP>
 bool launch_dma(int r, int variant, dim3 grid, dim3 block, size_t lds, hipStream_t s, const ActorArgs<real>& A,
                 const KParams<real>& P, hipEvent_t ev_a, hipEvent_t ev_b);

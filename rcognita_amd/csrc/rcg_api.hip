@@ -1354,6 +1354,12 @@ int rcg_last_launch(const rcg_handle* h, int32_t kind, int32_t* kernel_id, int32
   return RCG_OK;
 }
 
+int rcg_last_launch_zero_w(const rcg_handle* h, int32_t kind, uint32_t* mask) {
+  if (!h || !mask || kind < 0 || kind >= RCG_KERNEL_COUNT_) return RCG_ERR_BAD_ARG;
+  *mask = h->last[kind].zero_w;
+  return RCG_OK;
+}
+
 const char* rcg_kernel_name(int32_t kernel_id) {
   static const char* const names[RCG_KID_COUNT_] = {"none",        "k_actor",   "k_actor_dma", "k_ticks",    "k_actor_opt",
                                                     "k_nominal",   "k_sim",     "k_sim_v",     "k_sim_dist", "k_critic_fit",

@@ -1,5 +1,5 @@
 // rcg_dma_launch.hpp - definition of launch_dma<Sys, real, GROUP> (declared in rcg_actor_dma.hpp): picks the
-// k_actor_dma<Sys, real, R, Sys::TGT, V> instance for a runtime row length and variant.  Included only by
+// k_actor_dma<Sys, real, R, Sys::TGT, V[, ZW]> instance for a runtime row length and variant.  Included only by
 // rcg_dma_inst.hip, which is compiled once per (system, element type, group): the ~700 kernel instances of the library
 // are spread over 36 objects that build in parallel.
 #pragma once
@@ -19,9 +19,9 @@ static bool launch_dma_r(int r, int variant, dim3 grid, dim3 block, size_t lds, 
     if constexpr (R % Sys::DU != 0) {
       return false;
     } else {
-#define RCG_DMA_CASE(V)                                                                                              \
-  case V: {                                                                                                          \
-    auto fn = k_actor_dma<Sys, real, R, ((V) >= DMA_MPC_GEND ? true : Sys::TGT), V>;                                 \
+#define RCG_DMA_LAUNCH(FN)                                                                                           \
+  {                                                                                                                  \
+    auto fn = FN;                                                                                                    \
     if (lds > 64 * 1024) /* f64 rows beyond 256 bytes: four 64-row tiles exceed the default dynamic-LDS limit */     \
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,       \
                                 (int)lds);                                                                           \
@@ -31,7 +31,15 @@ static bool launch_dma_r(int r, int variant, dim3 grid, dim3 block, size_t lds, 
       hipLaunchKernelGGL(fn, grid, block, lds, s, A, P);                                                             \
     return true;                                                                                                     \
   }
+#define RCG_DMA_CASE(V) \
+  case V:               \
+    RCG_DMA_LAUNCH((k_actor_dma<Sys, real, R, ((V) >= DMA_MPC_GEND ? true : Sys::TGT), V>))
       if constexpr (GROUP == 0) {
+        // the zero-weight instance of DMA_MPC_G1 (float64 robots; rcg_actor_dma.hpp): the same variant word, its own kernel
+        constexpr unsigned ZWP = dma_zw_preset<Sys, real>();
+        if constexpr (ZWP != 0u) {
+          if (dma_zero_w<real>(ZWP, variant, A, P) != 0u) RCG_DMA_LAUNCH((k_actor_dma<Sys, real, R, Sys::TGT, DMA_MPC_G1, ZWP>))
+        }
         switch (variant) {
           RCG_DMA_CASE(DMA_MPC_G1)
           RCG_DMA_CASE(DMA_MPC)
@@ -64,6 +72,7 @@ static bool launch_dma_r(int r, int variant, dim3 grid, dim3 block, size_t lds, 
         }
       }
 #undef RCG_DMA_CASE
+#undef RCG_DMA_LAUNCH
       return false;
     }
   }

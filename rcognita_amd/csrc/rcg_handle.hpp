@@ -85,6 +85,7 @@ struct rcg_handle {
   // rcg_last_launch: which kernel served the last launch of each kind
   struct LastLaunch {
     int32_t kernel_id, variant, envs_per_wave;
+    uint32_t zero_w;  // rcg_last_launch_zero_w: the chi components whose cost terms the instance skipped (k_actor_dma), else 0
   } last[RCG_KERNEL_COUNT_];
 };
 static constexpr size_t kProfMaxSamples = 65536;
@@ -96,6 +97,7 @@ static inline void note_launch(rcg_handle* h, int kind, int kernel_id, int varia
   h->last[kind].kernel_id = kernel_id;
   h->last[kind].variant = variant | (h->sub_hi > 0 ? kVariantSplitBit : 0);
   h->last[kind].envs_per_wave = envs_per_wave;
+  h->last[kind].zero_w = 0u;  // (the k_actor_dma launchers set it behind this call)
 }
 
 // [0,392) R1|R2 as f32, [512,1296) R1|R2 as f64, [1296,2256) w_init|w_min|w_max as f64

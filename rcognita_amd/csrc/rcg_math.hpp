@@ -166,6 +166,52 @@ __device__ __forceinline__ unsigned long long wave_min_u64(unsigned long long k)
   return b < a ? b : a;
 }
 
+// The same four DPP stages and three scalar-side mins on a double (its two halves travel as the key's do; `<` on values
+// that are never NaN) and on a 32-bit key: k_actor_dma's float64 argmin minimises the cost first and then, among the lanes
+// that hold the minimum, the candidate index - a float64 cost and an index do not fit one 64-bit key.
+__device__ __forceinline__ double wave_min_f64(double v) {
+#define RCG_DPP_MIN(CTRL)                                                                                          \
+  {                                                                                                                \
+    const unsigned long long k = (unsigned long long)__double_as_longlong(v);                                      \
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, CTRL, 0xF, 0xF, false);         \
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xF, 0xF, false); \
+    const double o = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));                       \
+    v = o < v ? o : v;                                                                                             \
+  }
+  RCG_DPP_MIN(0xB1)   // quad_perm [1,0,3,2]
+  RCG_DPP_MIN(0x4E)   // quad_perm [2,3,0,1]
+  RCG_DPP_MIN(0x141)  // row_half_mirror
+  RCG_DPP_MIN(0x140)  // row_mirror
+#undef RCG_DPP_MIN
+  double r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned long long k = (unsigned long long)__double_as_longlong(v);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, 16 * i);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), 16 * i);
+    r[i] = __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
+  }
+  const double a = r[1] < r[0] ? r[1] : r[0], b = r[3] < r[2] ? r[3] : r[2];
+  return b < a ? b : a;
+}
+__device__ __forceinline__ unsigned wave_min_u32(unsigned k) {
+#define RCG_DPP_MIN(CTRL)                                                                        \
+  {                                                                                              \
+    const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(0, (int)k, CTRL, 0xF, 0xF, false); \
+    k = o < k ? o : k;                                                                           \
+  }
+  RCG_DPP_MIN(0xB1)
+  RCG_DPP_MIN(0x4E)
+  RCG_DPP_MIN(0x141)
+  RCG_DPP_MIN(0x140)
+#undef RCG_DPP_MIN
+  unsigned r[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) r[i] = (unsigned)__builtin_amdgcn_readlane((int)k, 16 * i);
+  const unsigned a = r[1] < r[0] ? r[1] : r[0], b = r[3] < r[2] ? r[3] : r[2];
+  return b < a ? b : a;
+}
+
 // v_readlane of a real (the lane index is wave-uniform)
 __device__ __forceinline__ float readlane_r(float v, int l) {
   return __uint_as_float((unsigned)__builtin_amdgcn_readlane((int)__float_as_uint(v), l));

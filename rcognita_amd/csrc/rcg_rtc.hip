@@ -47,8 +47,9 @@ struct RtcSystem {
   std::string name, src;
   RtcDims dims;
   bool tgt;                 // the policy's TGT (default false): which k_actor_dma instance serves a handle with a target
+  unsigned zw;              // the policy's ZW_PRESET (default 0): the zero-weight instance of k_actor_dma's DMA_MPC_G1 (float64)
   RtcProgram core[2];       // [0] float, [1] double
-  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant)
+  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant | 256: zero-weight instance)
   std::map<std::tuple<int, int, int>, std::unique_ptr<RtcProgram>> critic;    // (f64, critic structure, FIT_FORM_*)
   std::vector<std::string> compiled;  // "<program>\t<name expression>" of everything compiled so far (rcg_system_programs)
 };
@@ -108,7 +109,7 @@ std::string unit_source(const RtcSystem& S, bool critic = false) {
          "template <class S> struct dy<S, void_t<decltype(S::DY)>> { static constexpr int v = S::DY; };\n"
          "template <class S, class = void> struct crit { static constexpr bool v = false; };\n"
          "template <class S> struct crit<S, void_t<decltype(S::CRITIC)>> { static constexpr bool v = S::CRITIC; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT> __global__ void k_rtc_probe() {}\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, unsigned ZW> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -195,12 +196,14 @@ std::string expr_opt(bool tgt, bool gen, bool pairs) {
   return std::string("rcg::k_actor_opt<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ", " + tf(gen) + ", " + tf(pairs) +
          ">";
 }
-// k_actor_dma's TGT parameter is the system's own for the preset-cost variants, true for DMA_MPC_GEND / GENF (rcg_dma_launch.hpp)
+// k_actor_dma's TGT parameter is the system's own for the preset-cost variants, true for DMA_MPC_GEND / GENF (rcg_dma_launch.hpp);
+// zw != 0: the zero-weight instance of DMA_MPC_G1 (rcg_actor_dma.hpp::dma_zero_w) - a registered copy of a robot resolves to
+// the instance the built-in one runs
 template <typename real>
-std::string expr_dma(bool packed, int R, int variant, bool sys_tgt) {
+std::string expr_dma(bool packed, int R, int variant, bool sys_tgt, unsigned zw) {
   const bool tgt = (!packed && variant >= DMA_MPC_GEND) ? true : sys_tgt;
   return std::string(packed ? "rcg::k_actor_dma_packed<" : "rcg::k_actor_dma<") + kSysExpr + ", " + real_name<real>() + ", " +
-         std::to_string(R) + ", " + tf(tgt) + ", " + std::to_string(variant) + ">";
+         std::to_string(R) + ", " + tf(tgt) + ", " + std::to_string(variant) + (zw ? ", " + std::to_string(zw) + "u>" : ">");
 }
 
 template <typename real>
@@ -276,15 +279,15 @@ int core_function(rcg_handle* h, const std::string& expr, hipFunction_t* fn) {
 // k_actor_dma / k_actor_dma_packed at the handle's row length: compiled the first time a handle of this (system, element type)
 // asks for it - outside the lock, so that launches of other handles do not wait for the compiler - then cached
 template <typename real>
-int dma_function(rcg_handle* h, bool packed, int R, int variant, hipFunction_t* fn) {
+int dma_function(rcg_handle* h, bool packed, int R, int variant, unsigned zw, hipFunction_t* fn) {
   RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  const std::string expr = expr_dma<real>(packed, R, variant, S.tgt);
+  const std::string expr = expr_dma<real>(packed, R, variant, S.tgt, zw);
   auto hit = h->rtc_fn.find(expr);
   if (hit != h->rtc_fn.end()) {
     *fn = hit->second;
     return RCG_OK;
   }
-  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, packed ? 1 : 0, R, variant);
+  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, packed ? 1 : 0, R, variant | (zw ? 256 : 0));
   bool have;
   {
     std::lock_guard<std::mutex> lock(g_mu);
@@ -448,13 +451,16 @@ int rtc_sim_step(rcg_handle* h, int32_t n_substeps) {
 // that the shape goes on to k_actor_dma / k_actor, as launch_actor's does when launch_dma_packed finds no instance)
 struct ActorPick {
   bool packed, dma;
+  unsigned zero_w;  // k_actor_dma: the mask of the zero-weight instance, 0: the plain one
   hipFunction_t f;
 };
 template <typename real>
-int resolve_actor_instance(rcg_handle* h, const ActorPlan& L, bool streamed, ActorPick* p) {
+int resolve_actor_instance(rcg_handle* h, const ActorArgs<real>& A, const ActorPlan& L, bool streamed, ActorPick* p) {
   p->packed = L.pack_ok && !(L.variant >= DMA_RQL_0 && !packed_critic_ok(h->dc, (int)sizeof(real)));
   p->dma = !p->packed && L.dma_ok;
-  if (p->packed || p->dma) return dma_function<real>(h, p->packed, L.R, L.variant, &p->f);
+  const RtcSystem& S = *h->rtc;
+  p->zero_w = (p->dma && sizeof(real) == 8 && !S.dims.has_out) ? dma_zero_w<real>(S.zw, L.variant, A, params<real>(h)) : 0u;
+  if (p->packed || p->dma) return dma_function<real>(h, p->packed, L.R, L.variant, p->zero_w, &p->f);
   return core_function<real>(h, expr_actor<real>(L.long_row || L.generic, L.tgt, streamed, L.long_row), &p->f);
 }
 
@@ -476,7 +482,7 @@ int actor(rcg_handle* h, const char* who, const void* cand, int K, const void* o
   if (h->sub_hi > 0 && !(L.dma_ok && !L.pack_ok))
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: a split tick needs the k_actor_dma shape", who);
   ActorPick pick;
-  rc = resolve_actor_instance<real>(h, L, cand != nullptr, &pick);
+  rc = resolve_actor_instance<real>(h, A, L, cand != nullptr, &pick);
   if (rc) return rc;
   const bool packed = pick.packed, dma = pick.dma;
   hipFunction_t const f = pick.f;
@@ -499,7 +505,10 @@ int actor(rcg_handle* h, const char* who, const void* cand, int K, const void* o
     ActorArgs<real> Ad = dma_args(h, A, L);
     void* args[] = {&Ad, &P};
     rc = launch(h, f, L.dma_grid, dim3(256), L.dma_lds, args);
-    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, L.variant, (int)L.dma_gpw);
+    if (rc == RCG_OK) {
+      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, L.variant, (int)L.dma_gpw);
+      h->last[RCG_KERNEL_ACTOR].zero_w = pick.zero_w;
+    }
     return rc;
   }
   void* args[] = {&A, &P};
@@ -634,30 +643,30 @@ int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, i
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT> mangles its arguments as Lb0E / Lb1E and Li<n>E / Lin<n>E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
-                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v>";
+                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET>";
   RtcProgram P;
   const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[6];
+  long v[7];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 6 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 7 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
     if (neg) ++q;
     long x = 0;
     while (q < low.size() && isdigit((unsigned char)low[q])) x = 10 * x + (low[q++] - '0');
-    if ((t != 'b' && t != 'i') || q >= low.size() || low[q] != 'E') break;
+    if ((t != 'b' && t != 'i' && t != 'j') || q >= low.size() || low[q] != 'E') break;
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 6) {
+  if (n != 7) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -667,6 +676,7 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.has_out = v[3] != 0;
   S.dims.has_out_jac = S.dims.has_out && v[4] != 0;
   S.dims.has_critic = v[5] != 0;
+  S.zw = (unsigned)v[6];
   return RCG_OK;
 }
 
@@ -712,7 +722,7 @@ int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K) {
                                h->f[RCG_FIELD_ACTION], h->f[RCG_FIELD_BEST_J], (int32_t*)h->f[RCG_FIELD_BEST_IDX], true, false, A, L);
     if (rc2) return rc2;
     ActorPick pick;
-    return resolve_actor_instance<real>(h, L, cand != nullptr, &pick);
+    return resolve_actor_instance<real>(h, A, L, cand != nullptr, &pick);
   });
 }
 

@@ -732,6 +732,7 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
     if (!ok) prof_give_back(h, pp);
     if (ok) {  // (otherwise - unreachable for the rows dma_ok admits - k_actor below serves the tick: never refused half-way)
       note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, variant, (int)L.dma_gpw);
+      h->last[RCG_KERNEL_ACTOR].zero_w = dma_zero_w<real>(dma_zw_preset<Sys, real>(), variant, Ad, P);  // launch_dma's rule
       HIPCHK(h, hipGetLastError());
       return RCG_OK;
     }

@@ -885,3 +885,10 @@ class Engine:
         N.check(N.lib().rcg_last_launch(self._h, int(kind), C.byref(kid), C.byref(var), C.byref(epw)), self._h)
         return {"kernel": N.lib().rcg_kernel_name(kid.value).decode(), "kernel_id": kid.value, "variant": var.value & ~4096,
                 "envs_per_wave": epw.value, "split": bool(var.value & 4096)}  # split: one half of a tick in two halves
+
+    def last_launch_zero_w(self, kind=N.KERNEL_ACTOR):
+        """Mask of the ``chi = [y, u]`` components whose zero-weighted cost terms the last launch of a kind skipped
+        (rcg_last_launch_zero_w): the preset's mask on k_actor_dma's float64 zero-weight instance, else 0."""
+        m = C.c_uint32()
+        N.check(N.lib().rcg_last_launch_zero_w(self._h, int(kind), C.byref(m)), self._h)
+        return int(m.value)
