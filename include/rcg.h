@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 123 /* 122 + rcg_last_launch_zero_w (the zero-weight instance of the float64 streamed decision) */
+#define RCG_VERSION 124 /* 123 + rcg_system_has_search (the device search for a registered policy with SEARCH = true) */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -191,8 +191,8 @@ int rcg_device_count(void);
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
  * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  rcg_create
- * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_actor_search, rcg_control_ticks and rcg_loop_step return
- * RCG_ERR_UNSUPPORTED with the handle untouched.
+ * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_control_ticks and rcg_loop_step - and, without SEARCH (below),
+ * rcg_actor_search and rcg_control_tick_search - return RCG_ERR_UNSUPPORTED with the handle untouched.
  * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
  * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
  * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
@@ -200,7 +200,14 @@ int rcg_device_count(void);
  * observations [buffer_size][DY][B]; a tick pushes out(STATE).  The critic kernels are compiled the first time a handle needs
  * them (one program per element type, critic structure and fit form), before the call enqueues anything; a split tick
  * (rcg_set_tick_parts 2) is RCG_ERR_UNSUPPORTED for such a handle.  Without CRITIC rcg_create refuses RQL / SQL and the critic
- * operators return RCG_ERR_UNSUPPORTED, as above. */
+ * operators return RCG_ERR_UNSUPPORTED, as above.
+ * The device search: a policy opts in with `static constexpr bool SEARCH = true;` (optional, default false).  rcg_actor_search and
+ * rcg_control_tick_search then run on k_actor_search, the kernel the built-in systems run, which needs nothing of the policy
+ * beyond rhs (and out, if it has one: y_0 = out(STATE) for a tick, rollouts observe out(x)) - the way to decide on the device
+ * without writing jac_T.  The instance a handle needs (element type, stage-cost form, target, register rows at Nactor 3 / 5 /
+ * 10) is compiled as a program of its own the first time it is asked for, before the call enqueues anything (seconds; a
+ * compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error and the handle untouched); the opt-in adds nothing to
+ * the registration itself.  RQL / SQL search needs CRITIC as well. */
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
@@ -214,8 +221,11 @@ int rcg_system_output_info(int32_t sys_id, int32_t* dy, int32_t* has_out, int32_
 /* whether a system runs the critic modes: 1 for the built-in ones and for a registered policy with CRITIC = true, else 0.
  * RCG_ERR_BAD_ARG for an id that names no system. */
 int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic);
+/* whether a system runs the device search (rcg_actor_search, rcg_control_tick_search): 1 for the built-in ones and for a
+ * registered policy with SEARCH = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system. */
+int rcg_system_has_search(int32_t sys_id, int32_t* has_search);
 /* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
- * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs).  Writes at
+ * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs, k_actor_search instances).  Writes at
  * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
 int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 

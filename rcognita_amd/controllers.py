@@ -68,8 +68,9 @@ class CtrlOptPred:
                 "run on the native path and there is no CPU fallback")
         self.sys = sys_obj
         # a system compiled at run time (System.hip_policy): RQL / SQL when its policy opts in to the critic kernels
-        # (`static constexpr bool CRITIC = true;`), no device search, the optimiser only when the policy has jac_T (and
-        # out_jac_T, if it has an output map)
+        # (`static constexpr bool CRITIC = true;`), the device search when it opts in with `static constexpr bool SEARCH = true;`,
+        # the optimiser only when the policy has jac_T (and out_jac_T, if it has an output map); actor_opt='auto' takes the
+        # optimiser where there is one, else the search
         info = type(sys_obj)._hip_info if type(sys_obj).hip_policy is not None else None
         self._runtime_sys = info is not None
         self._has_out = bool(info is not None and info.get("has_out"))
@@ -78,12 +79,16 @@ class CtrlOptPred:
                 raise NotImplementedError(f"{type(sys_obj).__name__} is compiled from hip_policy: mode {mode!r} needs the critic "
                                           "kernels, which a policy opts in to with `static constexpr bool CRITIC = true;` "
                                           "(the built-in systems have them); use mode='MPC'")
-            has_opt = info["has_jac"] and (not info.get("has_out") or info.get("has_out_jac"))
-            if candidates is None and (actor_opt == "sampling" or not has_opt):
+            has_opt = bool(info["has_jac"] and (not info.get("has_out") or info.get("has_out_jac")))
+            has_search = bool(info.get("has_search"))
+            if candidates is None and ((actor_opt == "sampling" and not has_search) or
+                                       (actor_opt == "gradient" and not has_opt) or not (has_opt or has_search)):
                 raise NotImplementedError(
-                    f"{type(sys_obj).__name__} is compiled from hip_policy: the device search (actor_opt='sampling') is not "
-                    "available for it, and the on-device optimiser needs jac_T in the policy (and out_jac_T with an output "
-                    "map out); pass candidates=")
+                    f"{type(sys_obj).__name__} is compiled from hip_policy: the device search (actor_opt='sampling') needs the "
+                    "policy to opt in with `static constexpr bool SEARCH = true;`, and the on-device optimiser needs jac_T in "
+                    "the policy (and out_jac_T with an output map out); add one of them or pass candidates=")
+            if actor_opt == "auto" and not has_opt and has_search:
+                actor_opt = "sampling"
         self.dim_input, self.dim_output = dim_input, dim_output
         self.mode = mode
         self.ctrl_clock = t0

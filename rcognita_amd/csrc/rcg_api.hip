@@ -1140,16 +1140,19 @@ int rcg_control_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t wa
   if (!h) return RCG_ERR_BAD_ARG;
   int rc = check_search(h, "rcg_control_tick_search", K, rounds);
   if (rc) return rc;
-  // (no device search for a system registered at run time: refused here, before the critic phase of an RQL / SQL tick runs)
-  if (h->rtc)
-    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_search: not available for a system registered at run time");
+  const bool warm = warm_start && h->tick_count > 0;
+  // (a system registered at run time: refused without SEARCH, else the tick's instances resolved - compiled on first use -
+  // here, before the critic phase of an RQL / SQL tick or the env step runs)
+  if (h->rtc) {
+    rc = rtc_prepare_tick_search(h, K, rounds, warm ? 1 : 0);
+    if (rc) return rc;
+  }
   bool sim_first = true;
   if (h->cfg.mode != RCG_MODE_MPC) {
     rc = tick_critic_phase(h, "rcg_control_tick_search");
     if (rc) return rc;
     sim_first = false;
   }
-  const bool warm = warm_start && h->tick_count > 0;
   void* sqn = h->f[RCG_FIELD_ACTION_SQN];
   rc = h->sys->search(h, K, rounds, 0, nullptr, nullptr, warm ? sqn : nullptr, warm ? 1 : 0, sqn, h->f[RCG_FIELD_ACTION],
                       h->f[RCG_FIELD_BEST_J], (int32_t*)h->f[RCG_FIELD_BEST_IDX], true, sim_first);

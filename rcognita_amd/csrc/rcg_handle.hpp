@@ -274,6 +274,7 @@ struct RtcDims {
   bool has_out;      // the policy defines out (y = out(x)); without it y = x
   bool has_out_jac;  // ... and out_jac_T, which k_actor_opt needs when there is an output map
   bool has_critic;   // the policy opts in to the critic kernels (static constexpr bool CRITIC = true): RQL / SQL handles
+  bool has_search;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])
@@ -282,6 +283,8 @@ int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n);
 // decision instance of this (cand, K) BEFORE the tick enqueues anything, so that a compile failure leaves the handle as it was
 int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K);
 int rtc_prepare_tick_opt(rcg_handle* h);  // ... and rcg_control_tick_opt
+// ... and rcg_control_tick_search (every mode): refuses a policy without SEARCH, else resolves the tick's search instance
+int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t warm);
 extern const SysVTable kVtRtc;
 // sets the thread's error text (rcg_last_error(NULL)) without rcg_fail's length limit: hipRTC's log
 void rcg_set_thread_error(const std::string& text);

@@ -11,11 +11,13 @@
 //   on first use     k_actor_dma / k_actor_dma_packed at the handle's row length and variant: one small program each, cached;
 //                    for a policy that opts in with `static constexpr bool CRITIC = true`, the critic program of a handle's
 //                    (element type, critic structure, fit form): k_critic, k_critic_cost and the fit kernel fit_plan picks;
+//                    for a policy that opts in with `static constexpr bool SEARCH = true`, the one k_actor_search instance
+//                    search_plan picks for a handle (element type, generic, target, compile-time horizon): a program each;
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
-// The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan (rcg_sysops.hpp), the functions
-// the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
+// The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan (rcg_sysops.hpp),
+// the functions the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
 // RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC (rcg_create refuses RQL / SQL for
-// it), the nominal controllers, the device search, T ticks per launch and rcg_loop_step (rcg_create refuses the disturbance
+// it), the device search of a policy without SEARCH, the nominal controllers, T ticks per launch and rcg_loop_step (rcg_create refuses the disturbance
 // model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
 // and a handle keeps the functions it has resolved; nothing is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
@@ -51,6 +53,7 @@ struct RtcSystem {
   RtcProgram core[2];       // [0] float, [1] double
   std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant | 256: zero-weight instance)
   std::map<std::tuple<int, int, int>, std::unique_ptr<RtcProgram>> critic;    // (f64, critic structure, FIT_FORM_*)
+  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> search;  // (f64, generic, tgt, nc): k_actor_search
   std::vector<std::string> compiled;  // "<program>\t<name expression>" of everything compiled so far (rcg_system_programs)
 };
 
@@ -77,7 +80,7 @@ bool is_identifier(const char* s) {
 
 // The generated unit: the kernel headers, the policy (its own file name and line numbers in hipRTC's log), the adapter that
 // supplies the optional members and the checks of the declared dimensions.
-std::string unit_source(const RtcSystem& S, bool critic = false) {
+std::string unit_source(const RtcSystem& S, bool critic = false, bool search = false) {
   char dims[1536];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
@@ -88,6 +91,7 @@ std::string unit_source(const RtcSystem& S, bool critic = false) {
            S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str());
   const std::string& N = S.name;
   return std::string(critic ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_critic_fit_gen.hpp\"\n" : "") +
+         (search ? "#include \"rcg_search.hpp\"\n" : "") +
          "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
@@ -109,7 +113,9 @@ std::string unit_source(const RtcSystem& S, bool critic = false) {
          "template <class S> struct dy<S, void_t<decltype(S::DY)>> { static constexpr int v = S::DY; };\n"
          "template <class S, class = void> struct crit { static constexpr bool v = false; };\n"
          "template <class S> struct crit<S, void_t<decltype(S::CRITIC)>> { static constexpr bool v = S::CRITIC; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, unsigned ZW> __global__ void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct srch { static constexpr bool v = false; };\n"
+         "template <class S> struct srch<S, void_t<decltype(S::SEARCH)>> { static constexpr bool v = S::SEARCH; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, unsigned ZW> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -221,6 +227,12 @@ std::string expr_fit(int cs, int form) {
   if (form == FIT_FORM_GEN) return "rcg::k_critic_fit_gen" + head + ">";
   if (form == FIT_FORM_3ML) return "rcg::k_critic_fit_ml" + head + ", 3>";
   return "rcg::k_critic_fit" + head + ", " + std::to_string(form == FIT_FORM_3 ? 3 : kFitMaxRows) + ">";
+}
+// the k_actor_search instance of a plan (rcg_sysops.hpp::search_plan): the register-row instances take the policy's own TGT
+template <typename real>
+std::string expr_search(bool generic, bool tgt, int nc) {
+  return std::string("rcg::k_actor_search<") + kSysExpr + ", " + real_name<real>() + ", " + tf(generic) + ", " + tf(tgt) + ", " +
+         std::to_string(nc) + ">";
 }
 
 template <typename real>
@@ -364,6 +376,54 @@ int critic_functions(rcg_handle* h, int form, hipFunction_t* f_critic, hipFuncti
     h->rtc_fn[e[i]] = *out[i];
   }
   return RCG_OK;
+}
+
+// The k_actor_search instance of a plan: a program of its own, compiled the first time a handle of this (system, element type,
+// generic, tgt, nc) asks for it, as the k_actor_dma instances are, then cached.  A compile error is RCG_ERR_BAD_ARG with hipRTC's
+// log (the policy's source is at fault: a member the search instantiates for the first time).  dma_function and
+// critic_functions answer a compile error with RCG_ERR_HIP instead; they predate this and keep their code.
+template <typename real>
+int search_function(rcg_handle* h, const SearchPlan& L, hipFunction_t* fn) {
+  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
+  const bool tgt = L.tgt;  // (search_plan gives nc > 0 only where tgt == Sys::TGT)
+  const std::string expr = expr_search<real>(L.generic, tgt, L.nc);
+  auto hit = h->rtc_fn.find(expr);
+  if (hit != h->rtc_fn.end()) {
+    *fn = hit->second;
+    return RCG_OK;
+  }
+  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.generic ? 1 : 0, tgt ? 1 : 0, L.nc);
+  bool have;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    have = S.search.count(key) != 0;
+  }
+  const std::string file = S.name + "_search.hip";
+  std::unique_ptr<RtcProgram> P;
+  if (!have) {
+    P.reset(new RtcProgram);
+    std::string log;
+    const int rc = compile(unit_source(S, false, true), file, {expr}, P.get(), &log);
+    if (rc) {
+      h->err = "runtime system " + S.name + ": compiling " + expr + ": " + log;
+      return rc;
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = S.search.find(key);
+  if (it == S.search.end()) {  // (else another thread has published it meanwhile)
+    it = S.search.emplace(key, std::move(P)).first;
+    S.compiled.push_back(file + "\t" + expr);
+  }
+  const int rc = function(h, *it->second, expr, fn);
+  if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
+  return rc;
+}
+
+int refuse_search(rcg_handle* h, const char* who) {
+  return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                  "%s: not available for a system registered at run time whose policy does not opt in with SEARCH (%s)", who,
+                  h->rtc ? h->rtc->name.c_str() : "?");
 }
 
 int refuse_critic(rcg_handle* h, const char* who) {
@@ -634,28 +694,53 @@ int rtc_ticks(rcg_handle* h, int32_t, int32_t, const void*) { return refuse(h, "
 int rtc_rhs_full(rcg_handle* h, const void*, const void*, const void*, const void*, void*, void*, void*, int32_t, int32_t) {
   return refuse(h, "rcg_rhs_full");
 }
-int rtc_search(rcg_handle* h, int32_t, int32_t, int32_t, const void*, const void*, const void*, int, void*, void*, void*, int32_t*,
-               bool, bool) {
-  return refuse(h, "rcg_actor_search");
+// The device search: op_search's plan (search_plan) on the program compiled for its instance.  The instance is resolved - and
+// compiled, the first time - before anything is enqueued.
+int rtc_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const void* obs, const void* state_sys, const void* centre,
+               int shift, void* u_best, void* action, void* best_J, int32_t* best_idx, bool tick, bool sim_first) {
+  if (!h->rtc->dims.has_search) return refuse_search(h, "rcg_actor_search");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    const RtcSystem& S = *h->rtc;
+    SearchArgs<real> A;
+    SearchPlan L;
+    int rc = search_plan<real>(h, S.dims.du, S.tgt, K, rounds, round0, obs, state_sys, centre, shift, u_best, action, best_J,
+                               best_idx, tick, A, L);
+    if (rc) return rc;
+    hipFunction_t f;
+    rc = search_function<real>(h, L, &f);
+    if (rc) return rc;
+    if (tick && sim_first) {
+      rc = sim_step<real>(h, h->cfg.substeps_per_tick);
+      if (rc) return rc;
+    }
+    KParams<real> P = params<real>(h);
+    ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+    void* args[] = {&A, &P};
+    rc = launch(h, f, L.grid, L.block, L.lds, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_SEARCH, L.variant, 1);
+    return rc;
+  });
 }
 int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, int32_t, double*, double*, double) {
   return refuse(h, "rcg_loop_step");
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
-                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET>";
+                        "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
+                        ">::v, " + kSysExpr + "::ZW_PRESET>";
   RtcProgram P;
   const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[7];
+  long v[8];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 7 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 8 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -666,7 +751,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 7) {
+  if (n != 8) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -676,7 +761,8 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.has_out = v[3] != 0;
   S.dims.has_out_jac = S.dims.has_out && v[4] != 0;
   S.dims.has_critic = v[5] != 0;
-  S.zw = (unsigned)v[6];
+  S.dims.has_search = v[6] != 0;
+  S.zw = (unsigned)v[7];
   return RCG_OK;
 }
 
@@ -723,6 +809,33 @@ int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K) {
     if (rc2) return rc2;
     ActorPick pick;
     return resolve_actor_instance<real>(h, A, L, cand != nullptr, &pick);
+  });
+}
+
+// rcg_control_tick_search: the refusal of a policy without SEARCH, then every instance the tick launches - the search instance of
+// the tick's own plan and, RQL / SQL, the critic program's fit kernel - resolved, and compiled on first use, before the tick
+// enqueues anything: a compile failure leaves every field of the handle as it was
+int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t warm) {
+  if (!h->rtc->dims.has_search) return refuse_search(h, "rcg_control_tick_search");
+  if (h->cfg.mode != RCG_MODE_MPC) {
+    if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_tick_search");
+    const int rc = by_dtype(h, [&](auto r) {
+      hipFunction_t f;
+      return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
+    });
+    if (rc) return rc;
+  }
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    const RtcSystem& S = *h->rtc;
+    SearchArgs<real> A;
+    SearchPlan L;
+    void* sqn = h->f[RCG_FIELD_ACTION_SQN];
+    int rc = search_plan<real>(h, S.dims.du, S.tgt, K, rounds, 0, nullptr, nullptr, warm ? sqn : nullptr, warm ? 1 : 0, sqn,
+                               h->f[RCG_FIELD_ACTION], h->f[RCG_FIELD_BEST_J], (int32_t*)h->f[RCG_FIELD_BEST_IDX], true, A, L);
+    if (rc) return rc;
+    hipFunction_t f;
+    return search_function<real>(h, L, &f);
   });
 }
 
@@ -782,7 +895,7 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   std::unique_ptr<RtcSystem> S(new RtcSystem);
   S->name = name;
   S->src = policy_src;
-  S->dims = RtcDims{ds, du, np, false, ds, false, false, false};
+  S->dims = RtcDims{ds, du, np, false, ds, false, false, false, false};
   S->tgt = false;
   std::string log;
   rc = probe(*S, &log);
@@ -811,6 +924,14 @@ int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic) {
   if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_critic: bad sys_id %d", sys_id);
   if (has_critic) *has_critic = d.has_critic ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_search(int32_t sys_id, int32_t* has_search) {
+  RtcDims d{0, 0, 0, false, 0, false, false, true, true};  // (the built-in systems have every k_actor_search instance)
+  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_search: bad sys_id %d", sys_id);
+  if (has_search) *has_search = d.has_search ? 1 : 0;
   return RCG_OK;
 }
 

@@ -173,7 +173,7 @@ __device__ __forceinline__ real cand_element(const KParams<real>& P, const CandK
 
 template <typename real>
 struct SearchArgs {
-  const real* obs;        // [dy][B]
+  const real* obs;        // [dy][B], or [ds][B] (obs_x: y_0 = out(obs), ActorArgs)
   const real* state_sys;  // [ds][B]
   const real* pars_env;   // [np][B] or nullptr
   const real* w;          // [dc][B] (RQL / SQL)
@@ -189,6 +189,7 @@ struct SearchArgs {
   real u0[RCG_MAX_DU];    // action_sqn_init entry (controllers.py:973-978)
   int K, rounds, round0;  // candidates per round; rounds to run; number of the first one (sets sigma and the draw)
   int shift;              // centre_in is last tick's optimum: shift it by one step (last entry repeated)
+  int obs_x;              // as ActorArgs::obs_x: obs holds a state (a system with an output map only; wave-uniform)
   uint64_t seed;
   int64_t env_id_base;
 };
@@ -200,7 +201,7 @@ __host__ __device__ constexpr int search_lds_reals(int R, bool /*reg_rows*/) { r
 
 template <typename Sys, typename real, bool GENERIC, bool TGT, int NC>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NC > 0 && sizeof(real) == 4 ? 4 : 1))) void k_actor_search(const SearchArgs<real> A, const KParams<real> P) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
   constexpr int RC = NC * DU;  // 0: runtime horizon, rows in LDS
   constexpr int TPC = CandGeom<DU>::TPC;
   static_assert(NC == 0 || !GENERIC, "register rows: MPC with a diagonal stage cost");
@@ -218,13 +219,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NC > 0 && s
   real* const centre = static_cast<real*>(__builtin_assume_aligned(wave_lds + 64 * R, 16));
   real* const myrow = tile + (size_t)lane * R;
 
-  real y0[DS], xs[DS];
+  real y0[DY], xs[DS], on[sys_dxy<Sys>()];
+  if constexpr (HasOut<Sys>::value) {  // y_0 from the observation, or out(state) (obs_x)
+    load_obs_raw<Sys, real>(A.obs, A.obs_x, B, b, on);
 #pragma unroll
-  for (int c = 0; c < DS; ++c) {
-    y0[c] = A.obs[(long)c * B + b];
-    xs[c] = A.state_sys[(long)c * B + b];
+    for (int c = 0; c < DS; ++c) xs[c] = A.state_sys[(long)c * B + b];
+  } else {  // (no output map: the statements in their earlier order)
+#pragma unroll
+    for (int c = 0; c < DS; ++c) {
+      y0[c] = A.obs[(long)c * B + b];
+      xs[c] = A.state_sys[(long)c * B + b];
+    }
   }
   const auto pre = load_pre<Sys, real>(P, A.pars_env, b);
+  if constexpr (HasOut<Sys>::value) obs_of_raw<Sys, real>(pre, A.obs_x, on, y0);
   constexpr int DCMAX = GENERIC ? NCHI * (NCHI + 1) / 2 + NCHI : 1;
   real wreg[DCMAX];
   if (GENERIC) {

@@ -914,8 +914,88 @@ int op_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* state
   });
 }
 
+// longest horizon whose FLOAT64 search keeps its rows in registers.  Round 6, interleaved A/B on one device
+// (profiles/r06_ab_search_f64_rows.txt): at Nactor = 10 the register-row instance needs 256 VGPRs + 19 AGPRs (one wave per SIMD) and
+// takes 690 us per C2-shape round of 256, the LDS-row instance (124 VGPRs, four waves) 525 us; at Nactor = 5 registers win, 257 against 268.
+#ifndef RCG_SEARCH_F64_REG_ROWS
+#define RCG_SEARCH_F64_REG_ROWS 5
+#endif
+
+// k_actor_search's arguments and launch shape for the handle (the built-in systems' launcher below and rcg_rtc.hip, which
+// therefore pick the same instance, geometry and variant word for a registered copy of a built-in system)
+struct SearchPlan {
+  bool generic, tgt;  // the instance: k_actor_search<Sys, real, generic, tgt, nc> (nc > 0: tgt is the system's own TGT)
+  int nc;             // compile-time horizon of the register-row instances (3 / 5 / 10), 0: rows in LDS
+  int wpb;            // waves (= envs) per workgroup
+  size_t lds;
+  dim3 grid, block;
+  int variant;        // rcg_last_launch
+};
+
+// Fills A and L; refuses (nothing launched) a bad argument or rows beyond the LDS budget.  The caller (rcg_api.hip) has checked K
+// and the critic weights.
+template <typename real>
+static int search_plan(rcg_handle* h, int du, bool sys_tgt, int32_t K, int32_t rounds, int32_t round0, const void* obs,
+                       const void* state_sys, const void* centre, int shift, void* u_best, void* action, void* best_J,
+                       int32_t* best_idx, bool tick, SearchArgs<real>& A, SearchPlan& L) {
+  const rcg_cfg& c = h->cfg;
+  const KParams<real>& P = params<real>(h);
+  memset(&A, 0, sizeof A);
+  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
+  if (state_sys)
+    A.state_sys = (const real*)state_sys;
+  else if (obs)
+    A.state_sys = (const real*)obs;
+  else
+    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  A.obs_x = obs ? 0 : 1;  // as actor_plan
+  if (obs && !state_sys && h->dy != h->ds)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_search: an observation of dim_output %d != dim_state %d needs state_sys", h->dy,
+                    h->ds);
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
+  A.centre_in = (const real*)centre;
+  A.u_best = (real*)u_best;
+  A.action_out = (real*)action;
+  A.best_J = (real*)best_J;
+  A.best_idx = best_idx;
+  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
+  A.step_rw = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
+  A.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
+  A.step_idx = (const int32_t*)h->f[RCG_FIELD_STEP_IDX];
+  for (int i = 0; i < du; ++i) A.u0[i] = (real)c.action_init[i];
+  A.K = K;
+  A.rounds = rounds;
+  A.round0 = round0;
+  A.shift = shift;
+  A.seed = c.seed;
+  A.env_id_base = c.env_id_base;
+  const int R = c.n_actor * du;
+  const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
+  const bool tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  // register rows (compile-time horizon): MPC with a diagonal stage cost, the preset's target setting, Nactor 3 / 5 / 10
+  int nc = (!generic && tgt == sys_tgt && (c.n_actor == 3 || c.n_actor == 5 || c.n_actor == 10)) ? c.n_actor : 0;
+  if (sizeof(real) == 8 && nc > RCG_SEARCH_F64_REG_ROWS) nc = 0;  // (float64 rows of 20 reals: 256 VGPRs + AGPRs, one wave per SIMD)
+  int wpb = 4;  // waves (= envs) per workgroup
+  const size_t lds_wave = (size_t)search_lds_reals(R, nc > 0) * sizeof(real);
+  while (wpb > 1 && lds_wave * wpb > (size_t)64 * 1024) wpb >>= 1;
+  const size_t lds = lds_wave * wpb;
+  if (lds > (size_t)64 * 1024)  // (65 rows per wave: 126 doubles / 252 floats per row)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_actor_search: rows of %d reals need %zu B of LDS per wave (at most 65536)", R,
+                    lds_wave);
+  L.generic = generic;
+  L.tgt = tgt;
+  L.nc = nc;
+  L.wpb = wpb;
+  L.lds = lds;
+  L.grid = dim3(blocks_for(c.batch, wpb));
+  L.block = dim3(64 * wpb);
+  L.variant = (generic ? 1 : 0) | (tgt ? 2 : 0) | (nc > 0 ? 4 : 0);
+  return RCG_OK;
+}
+
 // rcg_actor_search / rcg_control_tick_search: `rounds` rounds of K generated candidates per env, evaluated where they are
-// generated (k_actor_search, rcg_search.hpp).  The caller (rcg_api.hip) has checked K and the critic weights.
+// generated (k_actor_search, rcg_search.hpp).
 template <typename Sys>
 int op_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const void* obs, const void* state_sys,
                      const void* centre, int shift, void* u_best, void* action, void* best_J, int32_t* best_idx, bool tick,
@@ -925,52 +1005,16 @@ int op_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const vo
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     SearchArgs<real> A;
-    memset(&A, 0, sizeof A);
-    A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
-    if (state_sys)
-      A.state_sys = (const real*)state_sys;
-    else if (obs)
-      A.state_sys = (const real*)obs;
-    else
-      A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-    A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
-    A.centre_in = (const real*)centre;
-    A.u_best = (real*)u_best;
-    A.action_out = (real*)action;
-    A.best_J = (real*)best_J;
-    A.best_idx = best_idx;
-    A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-    A.step_rw = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
-    A.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
-    A.step_idx = (const int32_t*)h->f[RCG_FIELD_STEP_IDX];
-    for (int i = 0; i < Sys::DU; ++i) A.u0[i] = (real)c.action_init[i];
-    A.K = K;
-    A.rounds = rounds;
-    A.round0 = round0;
-    A.shift = shift;
-    A.seed = c.seed;
-    A.env_id_base = c.env_id_base;
-    const int R = c.n_actor * Sys::DU;
-    const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
-    const bool tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
-    // register rows (compile-time horizon): MPC with a diagonal stage cost, the preset's target setting, Nactor 3 / 5 / 10
-// longest horizon whose FLOAT64 search keeps its rows in registers.  Round 6, interleaved A/B on one device
-// (profiles/r06_ab_search_f64_rows.txt): at Nactor = 10 the register-row instance needs 256 VGPRs + 19 AGPRs (one wave per SIMD) and
-// takes 690 us per C2-shape round of 256, the LDS-row instance (124 VGPRs, four waves) 525 us; at Nactor = 5 registers win, 257 against 268.
-#ifndef RCG_SEARCH_F64_REG_ROWS
-#define RCG_SEARCH_F64_REG_ROWS 5
-#endif
-    int nc = (!generic && tgt == Sys::TGT && (c.n_actor == 3 || c.n_actor == 5 || c.n_actor == 10)) ? c.n_actor : 0;
-    if (sizeof(real) == 8 && nc > RCG_SEARCH_F64_REG_ROWS) nc = 0;  // (float64 rows of 20 reals: 256 VGPRs + AGPRs, one wave per SIMD)
-    int wpb = 4;  // waves (= envs) per workgroup
-    const size_t lds_wave = (size_t)search_lds_reals(R, nc > 0) * sizeof(real);
-    while (wpb > 1 && lds_wave * wpb > (size_t)64 * 1024) wpb >>= 1;
-    const size_t lds = lds_wave * wpb;
-    if (lds > (size_t)64 * 1024)  // (65 rows per wave: 126 doubles / 252 floats per row)
-      return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_actor_search: rows of %d reals need %zu B of LDS per wave (at most 65536)", R,
-                      lds_wave);
-    const dim3 grid(blocks_for(c.batch, wpb)), block(64 * wpb);
+    SearchPlan L;
+    {
+      const int rc = search_plan<real>(h, Sys::DU, Sys::TGT, K, rounds, round0, obs, state_sys, centre, shift, u_best, action,
+                                       best_J, best_idx, tick, A, L);
+      if (rc) return rc;
+    }
+    const bool generic = L.generic, tgt = L.tgt;
+    const int nc = L.nc;
+    const dim3 grid = L.grid, block = L.block;
+    const size_t lds = L.lds;
     if (tick && sim_first) {
       const int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
       if (rc) return rc;
@@ -990,7 +1034,7 @@ int op_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const vo
       RCG_LAUNCH(h, (k_actor_search<Sys, real, false, true, 0>), grid, block, lds, A, P);
     else
       RCG_LAUNCH(h, (k_actor_search<Sys, real, false, false, 0>), grid, block, lds, A, P);
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_SEARCH, (generic ? 1 : 0) | (tgt ? 2 : 0) | (nc > 0 ? 4 : 0), 1);
+    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_SEARCH, L.variant, 1);
     HIPCHK(h, hipGetLastError());
     return (int)RCG_OK;
   });

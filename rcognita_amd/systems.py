@@ -14,7 +14,8 @@ Same class names, constructor signature and method names as the reference, so a 
   (SURVEY.md 8a row 1);
 * your own system: instead of overriding ``_state_dyn`` in Python, a subclass sets ``hip_policy`` to the source of a policy
   struct in the shape of the built-ins (rcognita_amd/csrc/rcg_systems.hpp).  The class is compiled for the GPU on its first
-  construction (``_native.register_system``) and runs the MPC path; INTEGRATION.md, "Your own system".
+  construction (``_native.register_system``) and runs the MPC path (RQL / SQL with ``CRITIC``, the device candidate search
+  with ``SEARCH`` in the policy); INTEGRATION.md, "Your own system".
 """
 from __future__ import annotations
 

@@ -10,9 +10,12 @@ DESIGN.md §13.1): its registration, its first streamed tick and its streamed f6
 RQL (policies with CRITIC): the first-use compile time of a critic program and of a DMA_RQL_* instance; the
 streamed f64 RQL tick of a Sys2Tank copy interleaved with the built-in Sys2Tank (the same code shape: any gap beyond the
 run-to-run spread is a finding); the same tick of the pendulum with the output map.
+The device search (policies with SEARCH): the first-use compile time of the k_actor_search program and the time
+of one rcg_control_tick_search round for the pendulum with and without the output map, f32 and f64, each next to the built-in
+Sys2Tank at the same shape.
 GPU box only; no torch.
 
-    python tools/user_system_probe.py [B] [K] [Nactor]
+    python tools/user_system_probe.py [B] [K] [Nactor] [search]      (search: that section alone)
 """
 import os
 import sys
@@ -84,6 +87,61 @@ B = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
 K = int(sys.argv[2]) if len(sys.argv) > 2 else 256
 NH = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 PEAK = 8e12
+ONLY = sys.argv[4] if len(sys.argv) > 4 else ""
+
+
+# ---- the device search on policies with SEARCH ---------------------------------------------------------------
+def with_search(src):
+    i = src.index("static constexpr int DS")
+    j = src.index("\n", i) + 1
+    return src[:j] + "  static constexpr bool SEARCH = true;\n" + src[j:]
+
+
+def search_rows():
+    pend = N.register_system("PendulumSearchProbe", with_search(PENDULUM.replace("PendulumT", "PendulumSearchProbe")), 2, 1, 3)
+    pout = N.register_system("PendulumOutSearchProbe", with_search(PENDULUM_OUT.replace("PendulumT", "PendulumOutSearchProbe")), 2, 1, 3)
+    assert pend["has_search"] and pout["has_search"]
+    rng = np.random.default_rng(1)
+    pb = np.array([[-5.0, 5.0]])
+    cases = (("pendulum (runtime)", pend["sys_id"], [1.3, 9.81, 0.7], np.diag([10.0, 1.0, 0.1]), None, pb, 0.01),
+             ("pendulum with out (runtime)", pout["sys_id"], [1.3, 9.81, 0.7], R1_OUT, None, pb, 0.01),
+             ("Sys2Tank (built-in)", N.SYS_2TANK, [18.4, 24.4, 1.3, 1.0, 0.2], np.diag([10.0, 10.0, 1.0]), [0.5, 0.5],
+              np.array([[0.0, 1.0]]), 0.1))
+    for dtype in ("f32", "f64"):
+        engines = []
+        for name, sid, pars, R1, tgt, bnds, dt in cases:
+            e = Engine(EngineConfig(sys_id=sid, batch=B, dtype=dtype, Nactor=NH, pars=pars, ctrl_bnds=bnds, R1=R1,
+                                    observation_target=tgt, dt_sim=dt, sampling_time=dt, pred_step_size=2 * dt))
+            e.set_state(rng.uniform(0, 1, (B, 2)))
+            t0 = time.perf_counter()
+            e.control_tick_search(K=K, rounds=1, warm_start=True)
+            e.synchronize()
+            first = time.perf_counter() - t0
+            n_prog = len([1 for _, x in N.system_programs(sid) if "k_actor_search" in x]) if sid >= N.SYS_USER_BASE else 0
+            for _ in range(5):
+                e.control_tick_search(K=K, rounds=1, warm_start=True)
+            e.synchronize()
+            e.profile([N.KERNEL_ACTOR])
+            engines.append((name, e, first, n_prog))
+        for _ in range(5):  # interleaved: ten ticks of each handle in turn
+            for name, e, first, n_prog in engines:
+                for _ in range(10):
+                    e.control_tick_search(K=K, rounds=1, warm_start=True)
+                e.synchronize()
+        for name, e, first, n_prog in engines:
+            t = e.profile_samples(N.KERNEL_ACTOR) * 1e-3
+            ll = e.last_launch()
+            blocks = np.median(t.reshape(5, -1), axis=1) * 1e6
+            print(f"search {dtype} {name:28s} {ll['kernel']} variant {ll['variant']}: first tick "
+                  f"{first:.2f} s ({'compiles the search program; ' + str(n_prog) + ' so far' if n_prog else 'nothing to compile'}), one round of "
+                  f"{K} at {B} envs x Nactor {NH}: {np.median(t) * 1e6:.1f} us (medians of the five blocks {blocks.min():.1f} .. "
+                  f"{blocks.max():.1f})")
+            e.close()
+
+
+if ONLY == "search":
+    search_rows()
+    sys.exit(0)
 
 info = N.register_system("PendulumProbe", PENDULUM.replace("PendulumT", "PendulumProbe"), 2, 1, 3)
 print(f"hiprtc {info['hiprtc']}: rcg_register_system {info['seconds']:.2f} s (probe + f32 + f64 core programs)")
@@ -199,3 +257,5 @@ for name, e, cand in engines:
           f"({B * K * NH * 8 / np.median(ta) / PEAK:.3f} of 8 TB/s; medians of the five blocks {blocks.min():.1f} .. {blocks.max():.1f}), "
           f"{lc['kernel']} variant {lc['variant']}: env step + push + fit {np.median(tc) * 1e6:.1f} us")
     e.close()
+
+search_rows()
