@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 124 /* 123 + rcg_system_has_search (the device search for a registered policy with SEARCH = true) */
+#define RCG_VERSION 125 /* 124 + rcg_system_has_ticks (T ticks per launch for a registered policy with TICKS = true) */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -191,8 +191,9 @@ int rcg_device_count(void);
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
  * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  rcg_create
- * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_control_ticks and rcg_loop_step - and, without SEARCH (below),
- * rcg_actor_search and rcg_control_tick_search - return RCG_ERR_UNSUPPORTED with the handle untouched.
+ * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_rhs_full and rcg_loop_step - and, without SEARCH (below),
+ * rcg_actor_search and rcg_control_tick_search, without TICKS (below) rcg_control_ticks - return RCG_ERR_UNSUPPORTED with the
+ * handle untouched.
  * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
  * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
  * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
@@ -207,7 +208,14 @@ int rcg_device_count(void);
  * without writing jac_T.  The instance a handle needs (element type, stage-cost form, target, register rows at Nactor 3 / 5 /
  * 10) is compiled as a program of its own the first time it is asked for, before the call enqueues anything (seconds; a
  * compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error and the handle untouched); the opt-in adds nothing to
- * the registration itself.  RQL / SQL search needs CRITIC as well. */
+ * the registration itself.  RQL / SQL search needs CRITIC as well.
+ * T ticks per launch: a policy opts in with `static constexpr bool TICKS = true;` (optional, default false).  rcg_control_ticks
+ * and the persistent path of rcg_control_tick_n then run on k_ticks (MPC) and k_ticks_mem (RQL / SQL, with CRITIC), the kernels
+ * the built-in systems run, under the same conditions and with the same launch shape; a tick observes out(STATE) if the policy
+ * has an output map.  The one instance a handle needs is compiled as a program of its own the first time it is asked for,
+ * before the call enqueues anything (a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error and the handle
+ * untouched); the opt-in adds nothing to the registration itself.  Without TICKS rcg_control_ticks is RCG_ERR_UNSUPPORTED and
+ * rcg_control_tick_n loops single ticks. */
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
@@ -224,8 +232,12 @@ int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic);
 /* whether a system runs the device search (rcg_actor_search, rcg_control_tick_search): 1 for the built-in ones and for a
  * registered policy with SEARCH = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system. */
 int rcg_system_has_search(int32_t sys_id, int32_t* has_search);
+/* whether a system runs T ticks per launch (rcg_control_ticks, the persistent path of rcg_control_tick_n): 1 for the built-in
+ * ones and for a registered policy with TICKS = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system. */
+int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks);
 /* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
- * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs, k_actor_search instances).  Writes at
+ * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs,
+ * k_actor_search instances, k_ticks / k_ticks_mem instances).  Writes at
  * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
 int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 
@@ -383,7 +395,10 @@ int rcg_control_tick(rcg_handle* h, const void* cand, int32_t K);
  * one persistent launch (k_ticks_mem), same functions on the same memory, bit-identical as well (critic structures with 20 or
  * more weights, whose single ticks fit with four lanes per env, run that four-lane walk as their critic phase; they need
  * K >= 4); other RQL / SQL handles get RCG_ERR_UNSUPPORTED and loop rcg_control_tick.  Removes the launch-bound regime of
- * small batches. */
+ * small batches.  A system registered at run time: only with TICKS = true in its policy (rcg_register_system; RQL / SQL: CRITIC
+ * as well), else RCG_ERR_UNSUPPORTED with the handle untouched.  Its instance is compiled on the first call, before anything is
+ * enqueued; a tick observes out(STATE); its k_ticks_mem instance is compiled for the handle's own target setting, so a target
+ * the policy's preset does not have is served too.  No k_ticks_pk shell for such a system: same bits from k_ticks. */
 int rcg_control_ticks(rcg_handle* h, int32_t T, int32_t K);
 /* T consecutive rcg_control_tick(h, cand, K) issued by ONE call: the loop of presets/main_3wrobot.py:415-468 for T sampling
  * periods with the SAME candidate tensor (or the generated grid, cand == NULL) at every tick, any mode.  Handles of up to
@@ -395,7 +410,8 @@ int rcg_control_ticks(rcg_handle* h, int32_t T, int32_t K);
  * the launches of T single ticks without T trips through the
  * caller's FFI (a Python caller needs ~12 us per call, and a GPU that idles between short ticks clocks down).  Either way
  * every field ends as T single calls leave it, bit for bit (Sys2Tank's BEST_J: to a rounding of its terms - see
- * rcg_control_ticks); stops at the first error. */
+ * rcg_control_ticks); stops at the first error.  A system registered at run time takes the persistent launches with TICKS = true
+ * in its policy and loops single ticks without it. */
 int rcg_control_tick_n(rcg_handle* h, const void* cand, int32_t K, int32_t T);
 /* A tick in two halves.  An RQL / SQL handle whose decision streams a caller's tensor through k_actor_dma (no disturbance
  * model, 1 .. 8 TD rows) runs rcg_control_tick for the envs [0, B / 2) and [B / 2, B) on two internal streams: the critic fit of

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "lib", "librcg.so")
 
 # ---- enums (include/rcg.h) -------------------------------------------------------------------
-RCG_VERSION = 124
+RCG_VERSION = 125
 OK, ERR_BAD_ARG, ERR_HIP, ERR_NO_DEVICE, ERR_UNSUPPORTED, ERR_NONFINITE = 0, -1, -2, -3, -4, -5
 SYS_3WROBOT, SYS_3WROBOT_NI, SYS_2TANK = 0, 1, 2
 MODE_MPC, MODE_RQL, MODE_SQL = 0, 1, 2
@@ -55,6 +55,7 @@ SYMBOLS = [
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
     "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit", "rcg_last_launch_zero_w", "rcg_system_has_search",
+    "rcg_system_has_ticks",
 ]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
@@ -190,6 +191,7 @@ def lib():
         "rcg_out": (C.c_int, [vp, vp, vp, i32]),
         "rcg_system_has_critic": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_system_has_search": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_system_has_ticks": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_critic_fit": (C.c_int, [vp]),
         "rcg_system_programs": (C.c_int, [i32, C.c_char_p, i64, C.POINTER(i64)]),
     }
@@ -215,10 +217,11 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search"}``: the id to put in ``rcg_cfg.sys_id``
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks"}``: the id to put in ``rcg_cfg.sys_id``
     (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
     optimiser), its dim_output ``DY``, whether it defines the output map ``out`` and its adjoint ``out_jac_T``, and whether it opts
-    in to the critic kernels (``CRITIC``: RQL / SQL) and to the device search (``SEARCH``: rcg_actor_search).  ``SYS_DIMS``
+    in to the critic kernels (``CRITIC``: RQL / SQL), to the device search (``SEARCH``: rcg_actor_search) and to T ticks per launch
+    (``TICKS``: rcg_control_ticks, the persistent path of rcg_control_tick_n).  ``SYS_DIMS``
     (``(ds, du, np)``) and ``SYS_DY`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
     the dimension limits)."""
     import time
@@ -240,9 +243,11 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     check(L.rcg_system_has_critic(sid.value, C.byref(crit)))
     srch = C.c_int32(0)
     check(L.rcg_system_has_search(sid.value, C.byref(srch)))
+    tck = C.c_int32(0)
+    check(L.rcg_system_has_ticks(sid.value, C.byref(tck)))
     return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
             "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value),
-            "has_critic": bool(crit.value), "has_search": bool(srch.value)}
+            "has_critic": bool(crit.value), "has_search": bool(srch.value), "has_ticks": bool(tck.value)}
 
 
 def system_programs(sys_id: int) -> list:

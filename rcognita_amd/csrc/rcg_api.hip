@@ -263,6 +263,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->du = du;
   h->np = np;
   h->rtc_has_out = rtc && rd.has_out;
+  h->rtc_has_ticks = rtc && rd.has_ticks;
   h->dy = rtc ? rd.dy : ds;  // R1 / R2 are (dy + du)^2 and the target has dy entries
   h->nchi = h->dy + du;
   h->dc = dim_critic(cfg->critic_struct, h->dy, du);  // the critic's regressor is over [y, u] (controllers.py:1192-1214)
@@ -873,8 +874,10 @@ static bool ticks_rows_stay_close(const rcg_handle* h, const void* cand, int32_t
 int rcg_control_tick_n(rcg_handle* h, const void* cand, int32_t K, int32_t T) {
   if (!h) return RCG_ERR_BAD_ARG;
   if (T < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_control_tick_n: T must be >= 1");
-  // (a system registered at run time has no k_ticks: the loop of single ticks below)
-  if (T > 1 && h->cfg.mode == RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch && !h->rtc &&
+  // (a system registered at run time has the persistent kernels only if its policy opts in with TICKS: without, the loop of
+  // single ticks below, on all three branches)
+  const bool persistent = !h->rtc || h->rtc_has_ticks;
+  if (T > 1 && h->cfg.mode == RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch && persistent &&
       ticks_rows_stay_close(h, cand, K)) {
     // MPC (any stage-cost structure, with or without the disturbance model): k_ticks keeps the env in registers and, for a
     // caller's tensor, the wave's candidate rows in LDS - every field ends as T single ticks leave it, bit for bit
@@ -885,13 +888,13 @@ int rcg_control_tick_n(rcg_handle* h, const void* cand, int32_t K, int32_t T) {
     if (rc == RCG_OK) h->tick_count += T;
     return rc;
   }
-  if (T > 1 && !cand && h->cfg.mode != RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch &&
+  if (T > 1 && !cand && h->cfg.mode != RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch && persistent &&
       h->cfg.n_critic - 1 >= 1 && h->cfg.n_critic - 1 <= kFitMaxRows && !(h->cfg.flags & RCG_FLAG_DISTURB)) {
     const int rc = rcg_control_ticks(h, T, K);  // RQL / SQL, generated grid: k_ticks_mem
     if (rc != RCG_ERR_UNSUPPORTED) return rc;  // (no instance for this observation target: the loop below)
     h->err.clear();  // the refusal was this function's own probe, not the caller's error (rcg_last_error after RCG_OK)
   }
-  if (T > 1 && cand && h->cfg.mode != RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch &&
+  if (T > 1 && cand && h->cfg.mode != RCG_MODE_MPC && h->cfg.batch <= kPersistentTicksMaxBatch && persistent &&
       h->cfg.n_critic - 1 >= 1 && h->cfg.n_critic - 1 <= kFitMaxRows && !(h->cfg.flags & RCG_FLAG_DISTURB) &&
       h->p32.stage_kind == 0 && ticks_rows_stay_close(h, cand, K)) {
     // RQL / SQL over a caller's tensor (round 5): k_ticks_mem with the streamed decision phase - the accumulation order of
@@ -920,6 +923,9 @@ int rcg_control_ticks(rcg_handle* h, int32_t T, int32_t K) {
   if (T < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_control_ticks: T must be >= 1");
   int rc = check_candidates(h, "rcg_control_ticks", nullptr, K);
   if (rc) return rc;
+  if (h->rtc && !h->rtc_has_ticks)  // (before the mode's own refusals: a policy without TICKS is refused by that name)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                    "rcg_control_ticks: not available for a system registered at run time whose policy does not opt in with TICKS");
   if (h->cfg.mode != RCG_MODE_MPC) {  // RQL / SQL: the launches of a tick as phases of one persistent launch
     const int m = h->cfg.n_critic - 1;
     if (m < 1 || m > kFitMaxRows || (h->cfg.flags & RCG_FLAG_DISTURB))

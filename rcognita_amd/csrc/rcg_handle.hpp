@@ -22,6 +22,7 @@ struct rcg_handle {
   int ds, du, np, dc, nchi;
   int dy;      // dim_output: ds, or the DY of a registered system with an output map (nchi = dy + du)
   bool rtc_has_out;  // a registered system with an output map (rcg_out launches k_out)
+  bool rtc_has_ticks;  // a registered system whose policy opts in with TICKS (k_ticks / k_ticks_mem compiled on first use)
   size_t esz;  // sizeof(real)
   hipStream_t stream;
   hipStream_t own_stream;  // created by rcg_use_own_stream, destroyed with the handle (nullptr: none)
@@ -275,6 +276,7 @@ struct RtcDims {
   bool has_out_jac;  // ... and out_jac_T, which k_actor_opt needs when there is an output map
   bool has_critic;   // the policy opts in to the critic kernels (static constexpr bool CRITIC = true): RQL / SQL handles
   bool has_search;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
+  bool has_ticks;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])

@@ -13,12 +13,15 @@
 //                    (element type, critic structure, fit form): k_critic, k_critic_cost and the fit kernel fit_plan picks;
 //                    for a policy that opts in with `static constexpr bool SEARCH = true`, the one k_actor_search instance
 //                    search_plan picks for a handle (element type, generic, target, compile-time horizon): a program each;
+//                    for a policy that opts in with `static constexpr bool TICKS = true`, the k_ticks instance ticks_plan picks
+//                    (element type, generic, target, streamed) and the k_ticks_mem instance ticks_mem_plan picks (element type,
+//                    critic structure, MAXM, target, four-lane fit, streamed): a program each;
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
-// The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan (rcg_sysops.hpp),
-// the functions the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
+// The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan / ticks_plan /
+// ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
 // RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC (rcg_create refuses RQL / SQL for
-// it), the device search of a policy without SEARCH, the nominal controllers, T ticks per launch and rcg_loop_step (rcg_create refuses the disturbance
-// model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
+// it), the device search of a policy without SEARCH, T ticks per launch of a policy without TICKS, the nominal controllers and
+// rcg_loop_step (rcg_create refuses the disturbance model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
 // and a handle keeps the functions it has resolved; nothing is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
 
@@ -54,6 +57,9 @@ struct RtcSystem {
   std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant | 256: zero-weight instance)
   std::map<std::tuple<int, int, int>, std::unique_ptr<RtcProgram>> critic;    // (f64, critic structure, FIT_FORM_*)
   std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> search;  // (f64, generic, tgt, nc): k_actor_search
+  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> ticks;   // (f64, generic, tgt, stream): k_ticks
+  // (f64, critic structure, MAXM, tgt | 2 ml | 4 stream): k_ticks_mem
+  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> ticks_mem;
   std::vector<std::string> compiled;  // "<program>\t<name expression>" of everything compiled so far (rcg_system_programs)
 };
 
@@ -80,7 +86,7 @@ bool is_identifier(const char* s) {
 
 // The generated unit: the kernel headers, the policy (its own file name and line numbers in hipRTC's log), the adapter that
 // supplies the optional members and the checks of the declared dimensions.
-std::string unit_source(const RtcSystem& S, bool critic = false, bool search = false) {
+std::string unit_source(const RtcSystem& S, bool critic = false, bool search = false, bool ticks = false) {
   char dims[1536];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
@@ -92,6 +98,7 @@ std::string unit_source(const RtcSystem& S, bool critic = false, bool search = f
   const std::string& N = S.name;
   return std::string(critic ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_critic_fit_gen.hpp\"\n" : "") +
          (search ? "#include \"rcg_search.hpp\"\n" : "") +
+         (ticks ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_ticks.hpp\"\n" : "") +
          "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
@@ -115,7 +122,10 @@ std::string unit_source(const RtcSystem& S, bool critic = false, bool search = f
          "template <class S> struct crit<S, void_t<decltype(S::CRITIC)>> { static constexpr bool v = S::CRITIC; };\n"
          "template <class S, class = void> struct srch { static constexpr bool v = false; };\n"
          "template <class S> struct srch<S, void_t<decltype(S::SEARCH)>> { static constexpr bool v = S::SEARCH; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, unsigned ZW> __global__ void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct tck { static constexpr bool v = false; };\n"
+         "template <class S> struct tck<S, void_t<decltype(S::TICKS)>> { static constexpr bool v = S::TICKS; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW> __global__ void "
+         "k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -124,6 +134,15 @@ std::string unit_source(const RtcSystem& S, bool critic = false, bool search = f
          "  static constexpr bool HAS_OUT = rtc::out<" + N + ">::v;\n"
          "  static constexpr int DY = rtc::dy<" + N + ">::v;\n"
          "};\n" +
+         // k_ticks names Disturb<Sys>: an inert one, shaped like Disturb<Sys2Tank> (rcg_create refuses the disturbance model for
+         // a registered system, so TicksArgs::dist is 0 and env_substeps_dist never runs)
+         (ticks ? "template <> struct Disturb<RcgRtcSys> {\n"
+                  "  static constexpr int DD = 1;\n"
+                  "  static constexpr bool inert = true;\n"
+                  "  template <typename real>\n"
+                  "  __device__ __forceinline__ static void apply(const RcgRtcSys::Pre<real>&, const real*, const real*, real*) {}\n"
+                  "};\n"
+                : "") +
          dims + "}  // namespace rcg\n";
 }
 
@@ -233,6 +252,18 @@ template <typename real>
 std::string expr_search(bool generic, bool tgt, int nc) {
   return std::string("rcg::k_actor_search<") + kSysExpr + ", " + real_name<real>() + ", " + tf(generic) + ", " + tf(tgt) + ", " +
          std::to_string(nc) + ">";
+}
+
+// the k_ticks / k_ticks_mem instance of a plan (rcg_sysops.hpp::ticks_plan, ticks_mem_plan)
+template <typename real>
+std::string expr_ticks(const TicksPlan& L) {
+  return std::string("rcg::k_ticks<") + kSysExpr + ", " + real_name<real>() + ", " + tf(L.generic) + ", " + tf(L.tgt) + ", " +
+         tf(L.stream) + ">";
+}
+template <typename real>
+std::string expr_ticks_mem(const TicksMemPlan& L) {
+  return std::string("rcg::k_ticks_mem<") + kSysExpr + ", " + real_name<real>() + ", " + std::to_string(L.cs) + ", " +
+         std::to_string(L.maxm) + ", " + tf(L.tgt) + ", " + tf(L.ml) + ", " + tf(L.stream) + ">";
 }
 
 template <typename real>
@@ -418,6 +449,49 @@ int search_function(rcg_handle* h, const SearchPlan& L, hipFunction_t* fn) {
   const int rc = function(h, *it->second, expr, fn);
   if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
   return rc;
+}
+
+// The k_ticks / k_ticks_mem instance of a plan: a program of its own, compiled the first time a handle of this system asks for the
+// key, as the k_actor_search instances are, then cached.  A compile error is RCG_ERR_BAD_ARG with hipRTC's log.
+int ticks_function(rcg_handle* h, bool mem, const std::tuple<int, int, int, int>& key, const std::string& expr, hipFunction_t* fn) {
+  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
+  auto hit = h->rtc_fn.find(expr);
+  if (hit != h->rtc_fn.end()) {
+    *fn = hit->second;
+    return RCG_OK;
+  }
+  auto& cache = mem ? S.ticks_mem : S.ticks;
+  bool have;
+  {
+    std::lock_guard<std::mutex> lock(g_mu);
+    have = cache.count(key) != 0;
+  }
+  const std::string file = S.name + (mem ? "_ticks_mem.hip" : "_ticks.hip");
+  std::unique_ptr<RtcProgram> P;
+  if (!have) {
+    P.reset(new RtcProgram);
+    std::string log;
+    const int rc = compile(unit_source(S, false, false, true), file, {expr}, P.get(), &log);
+    if (rc) {
+      h->err = "runtime system " + S.name + ": compiling " + expr + ": " + log;
+      return rc;
+    }
+  }
+  std::lock_guard<std::mutex> lock(g_mu);
+  auto it = cache.find(key);
+  if (it == cache.end()) {  // (else another thread has published it meanwhile)
+    it = cache.emplace(key, std::move(P)).first;
+    S.compiled.push_back(file + "\t" + expr);
+  }
+  const int rc = function(h, *it->second, expr, fn);
+  if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
+  return rc;
+}
+
+int refuse_ticks(rcg_handle* h, const char* who) {
+  return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                  "%s: not available for a system registered at run time whose policy does not opt in with TICKS (%s)", who,
+                  h->rtc ? h->rtc->name.c_str() : "?");
 }
 
 int refuse_search(rcg_handle* h, const char* who) {
@@ -690,7 +764,56 @@ int rtc_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_
 int rtc_nominal(rcg_handle* h, const void*, void*, void*, void*, int32_t, double, const double*, int32_t, bool) {
   return refuse(h, "the nominal controller");
 }
-int rtc_ticks(rcg_handle* h, int32_t, int32_t, const void*) { return refuse(h, "rcg_control_ticks"); }
+// T ticks in one launch: op_ticks' / op_ticks_mem's plan (ticks_plan, ticks_mem_plan) on the program compiled for its instance -
+// except the shell written for one built-in system (k_ticks_pk).  The instance is resolved - and compiled, the first time -
+// before anything is enqueued.
+int rtc_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
+  if (!h->rtc->dims.has_ticks) return refuse_ticks(h, "rcg_control_ticks");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    const RtcSystem& S = *h->rtc;
+    TicksArgs<real> A;
+    TicksPlan L;
+    int rc = ticks_plan<real>(h, S.dims.du, T, K, cand, A, L);
+    if (rc) return rc;
+    hipFunction_t f;
+    rc = ticks_function(h, false, std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.generic ? 1 : 0, L.tgt ? 1 : 0, L.stream ? 1 : 0),
+                        expr_ticks<real>(L), &f);
+    if (rc) return rc;
+    KParams<real> P = params<real>(h);
+    ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+    // (an LDS request beyond 64 KB - the rows of four waves resident for all T ticks - goes into the module launch as it is,
+    // as k_actor_dma's does: rtc_optimize)
+    void* args[] = {&A, &P};
+    rc = launch(h, f, L.grid, L.block, L.lds, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, A.G);
+    return rc;
+  });
+}
+int rtc_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
+  if (!h->rtc->dims.has_ticks) return refuse_ticks(h, "rcg_control_ticks");
+  if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_ticks");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    const RtcSystem& S = *h->rtc;
+    TicksMemArgs<real> M;
+    TicksMemPlan L;
+    int rc = ticks_mem_plan<real>(h, S.dims.du, S.tgt, true, T, K, cand, M, L);
+    if (rc) return rc;
+    hipFunction_t f;
+    rc = ticks_function(h, true,
+                        std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.cs, L.maxm, (L.tgt ? 1 : 0) | (L.ml ? 2 : 0) | (L.stream ? 4 : 0)),
+                        expr_ticks_mem<real>(L), &f);
+    if (rc) return rc;
+    KParams<double> P64 = h->p64;
+    KParams<real> P = params<real>(h);
+    ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+    void* args[] = {&M, &P64, &P};
+    rc = launch(h, f, L.grid, L.block, L.lds, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, M.A.G);
+    return rc;
+  });
+}
 int rtc_rhs_full(rcg_handle* h, const void*, const void*, const void*, const void*, void*, void*, void*, int32_t, int32_t) {
   return refuse(h, "rcg_rhs_full");
 }
@@ -727,20 +850,20 @@ int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, i
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
-                        ">::v, " + kSysExpr + "::ZW_PRESET>";
+                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET>";
   RtcProgram P;
   const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[8];
+  long v[9];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 8 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 9 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -751,7 +874,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 8) {
+  if (n != 9) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -762,7 +885,8 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.has_out_jac = S.dims.has_out && v[4] != 0;
   S.dims.has_critic = v[5] != 0;
   S.dims.has_search = v[6] != 0;
-  S.zw = (unsigned)v[7];
+  S.dims.has_ticks = v[7] != 0;
+  S.zw = (unsigned)v[8];
   return RCG_OK;
 }
 
@@ -771,7 +895,7 @@ int probe(RtcSystem& S, std::string* log) {
 #if !defined(__HIP_DEVICE_COMPILE__)  // (the table of host function pointers exists in the host pass only)
 const SysVTable kVtRtc = {&rtc_rhs,     &rtc_stage_obj, &rtc_critic,   &rtc_critic_cost, &rtc_actor,
                           &rtc_sim_step, &rtc_critic_update, &rtc_optimize, &rtc_nominal, &rtc_ticks,
-                          &rtc_rhs_full, &rtc_search,    &rtc_ticks,    &rtc_loop};
+                          &rtc_rhs_full, &rtc_search,    &rtc_ticks_mem, &rtc_loop};
 #endif
 
 int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
@@ -895,7 +1019,7 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   std::unique_ptr<RtcSystem> S(new RtcSystem);
   S->name = name;
   S->src = policy_src;
-  S->dims = RtcDims{ds, du, np, false, ds, false, false, false, false};
+  S->dims = RtcDims{ds, du, np, false, ds, false, false, false, false, false};
   S->tgt = false;
   std::string log;
   rc = probe(*S, &log);
@@ -932,6 +1056,14 @@ int rcg_system_has_search(int32_t sys_id, int32_t* has_search) {
   if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_search: bad sys_id %d", sys_id);
   if (has_search) *has_search = d.has_search ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks) {
+  RtcDims d{0, 0, 0, false, 0, false, false, true, true, true};  // (the built-in systems have every k_ticks / k_ticks_mem instance)
+  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
+    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_ticks: bad sys_id %d", sys_id);
+  if (has_ticks) *has_ticks = d.has_ticks ? 1 : 0;
   return RCG_OK;
 }
 

@@ -1040,69 +1040,97 @@ int op_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const vo
   });
 }
 
+// k_ticks' arguments and launch shape for the handle, from runtime values alone (the built-in systems' launcher below and
+// rcg_rtc.hip, which therefore pick the same instance, geometry and variant word for a registered copy of a built-in system)
+struct TicksPlan {
+  bool generic, tgt, stream;  // the instance: k_ticks<Sys, real, generic, tgt, stream>
+  size_t lds;
+  dim3 grid, block;
+  int variant;                // rcg_last_launch
+};
+
+// Fills A and L.  The caller (rcg_api.hip) has checked mode / K.
+template <typename real>
+static int ticks_plan(rcg_handle* h, int DU, int32_t T, int32_t K, const void* cand, TicksArgs<real>& A, TicksPlan& L) {
+  const rcg_cfg& c = h->cfg;
+  const KParams<real>& P = params<real>(h);
+  memset(&A, 0, sizeof A);
+  A.state = (real*)h->f[RCG_FIELD_STATE];
+  A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  A.action = (real*)h->f[RCG_FIELD_ACTION];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
+  A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  A.best_J = (real*)h->f[RCG_FIELD_BEST_J];
+  A.best_idx = (int32_t*)h->f[RCG_FIELD_BEST_IDX];
+  A.cand = (const real*)cand;
+  A.dist = (c.flags & RCG_FLAG_DISTURB) ? 1 : 0;
+  if (A.dist) {
+    A.disturb = (real*)h->f[RCG_FIELD_DISTURB];
+    A.substep_idx = (int32_t*)h->f[RCG_FIELD_SUBSTEP_IDX];
+    A.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
+    A.D = disturb_pars(h);
+  }
+  A.T = T;
+  A.n_sub = c.substeps_per_tick;
+  A.K = K;
+  if (K >= 64) {  // the tiling of launch_actor
+    A.Kp = 64;
+    A.G = 1;
+    A.n_tiles = (K + 63) / 64;
+  } else {
+    int kp = 1;
+    while (kp < K) kp <<= 1;
+    A.Kp = kp;
+    A.G = 64 / kp;
+    A.n_tiles = 1;
+  }
+  A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
+  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+  const long n_waves = (c.batch + A.G - 1) / A.G;
+  L.generic = P.stage_kind != 0;
+  L.tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  L.stream = cand != nullptr;
+  // streamed candidates: the wave's rows stay in LDS for all T ticks when they fit (32 KB per wave: four waves per block,
+  // one block per CU at worst), else they are re-staged tile by tile every tick (served by L2 / Infinity Cache at the
+  // batch sizes this entry point is for)
+  const int R = c.n_actor * DU;
+  const size_t row_bytes = (size_t)R * sizeof(real);
+  size_t lds = 0;
+  if (cand) {
+    const size_t rows_wave = K >= 64 ? (size_t)K : (size_t)A.G * K;
+    A.vec_ok = (row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
+    A.stage_once = rows_wave * row_bytes <= (size_t)32 * 1024 ? 1 : 0;
+    const size_t per_wave = (A.stage_once ? rows_wave : (size_t)64) * row_bytes;
+    A.lds_reals = (int)((per_wave + 15) / 16 * 16 / sizeof(real));
+    lds = (size_t)A.lds_reals * sizeof(real) * 4;
+  }
+  L.lds = lds;
+  L.grid = dim3((unsigned)((n_waves + 3) / 4));
+  L.block = dim3(256);
+  L.variant = (L.generic ? 1 : 0) | (L.tgt ? 2 : 0) | (cand ? 4 : 0);
+  return RCG_OK;
+}
+
 // rcg_control_ticks / rcg_control_tick_n: T MPC ticks in one launch (k_ticks, k_ticks_pk; rcg_ticks.hpp), generated grid
 // (cand == nullptr) or the caller's candidate tensor, with or without the disturbance model.  The caller has checked
 // mode / K.
 template <typename Sys>
 int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
-  constexpr int DU = Sys::DU;
   const rcg_cfg& c = h->cfg;
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     TicksArgs<real> A;
-    memset(&A, 0, sizeof A);
-    A.state = (real*)h->f[RCG_FIELD_STATE];
-    A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-    A.action = (real*)h->f[RCG_FIELD_ACTION];
-    A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    A.accum = (real*)h->f[RCG_FIELD_ACCUM];
-    A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
-    A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-    A.best_J = (real*)h->f[RCG_FIELD_BEST_J];
-    A.best_idx = (int32_t*)h->f[RCG_FIELD_BEST_IDX];
-    A.cand = (const real*)cand;
-    A.dist = (c.flags & RCG_FLAG_DISTURB) ? 1 : 0;
-    if (A.dist) {
-      A.disturb = (real*)h->f[RCG_FIELD_DISTURB];
-      A.substep_idx = (int32_t*)h->f[RCG_FIELD_SUBSTEP_IDX];
-      A.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
-      A.D = disturb_pars(h);
+    TicksPlan L;
+    {
+      const int rc = ticks_plan<real>(h, Sys::DU, T, K, cand, A, L);
+      if (rc) return rc;
     }
-    A.T = T;
-    A.n_sub = c.substeps_per_tick;
-    A.K = K;
-    if (K >= 64) {  // the tiling of launch_actor
-      A.Kp = 64;
-      A.G = 1;
-      A.n_tiles = (K + 63) / 64;
-    } else {
-      int kp = 1;
-      while (kp < K) kp <<= 1;
-      A.Kp = kp;
-      A.G = 64 / kp;
-      A.n_tiles = 1;
-    }
-    A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
-    A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
-    const long n_waves = (c.batch + A.G - 1) / A.G;
-    const bool generic = P.stage_kind != 0;
-    const bool tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
-    // streamed candidates: the wave's rows stay in LDS for all T ticks when they fit (32 KB per wave: four waves per block,
-    // one block per CU at worst), else they are re-staged tile by tile every tick (served by L2 / Infinity Cache at the
-    // batch sizes this entry point is for)
-    const int R = c.n_actor * DU;
-    const size_t row_bytes = (size_t)R * sizeof(real);
-    size_t lds = 0;
-    if (cand) {
-      const size_t rows_wave = K >= 64 ? (size_t)K : (size_t)A.G * K;
-      A.vec_ok = (row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
-      A.stage_once = rows_wave * row_bytes <= (size_t)32 * 1024 ? 1 : 0;
-      const size_t per_wave = (A.stage_once ? rows_wave : (size_t)64) * row_bytes;
-      A.lds_reals = (int)((per_wave + 15) / 16 * 16 / sizeof(real));
-      lds = (size_t)A.lds_reals * sizeof(real) * 4;
-    }
-    const dim3 grid((unsigned)((n_waves + 3) / 4)), block(256);
+    const bool generic = L.generic, tgt = L.tgt;
+    const size_t lds = L.lds;
+    const dim3 grid = L.grid, block = L.block;
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
     if constexpr (std::is_same<real, float>::value && GenPk<Sys>::supported) {
       const bool pk_ok = !cand && !A.dist && !generic && !tgt && c.gamma == 1.0 && Sys::ZW_PRESET != 0u &&
@@ -1148,87 +1176,125 @@ int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     else
       RCG_TICKS(false, false);
 #undef RCG_TICKS
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, (generic ? 1 : 0) | (tgt ? 2 : 0) | (cand ? 4 : 0), A.G);
+    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, A.G);
     HIPCHK(h, hipGetLastError());
     return (int)RCG_OK;
   });
 }
 
-// rcg_control_ticks on an RQL / SQL handle: T ticks in one launch (k_ticks_mem), generated candidates.  The caller has
-// checked K, the critic buffers, 1 <= Ncritic - 1 <= kFitMaxRows, no disturbance model, and that an instance exists
-// (ticks_mem_ok).
-template <typename Sys>
-static bool ticks_mem_ok(const rcg_handle* h) {
+// k_ticks_mem's arguments and launch shape for the handle, and its refusals (nothing launched) - shared, as ticks_plan is, by the
+// built-in systems' launcher below and rcg_rtc.hip.  `sys_tgt`: the system's preset target setting; `any_tgt`: the caller can
+// produce the instance of either target setting (a system compiled at run time compiles the one its generated-grid single ticks
+// run; the built-in systems pre-compile the preset's, whose zeros also serve a handle without a target).
+struct TicksMemPlan {
+  int cs, maxm;           // the instance: k_ticks_mem<Sys, real, cs, maxm, tgt, ml, stream>
+  bool tgt, ml, stream;
+  size_t lds;
+  dim3 grid, block;
+  int variant;            // rcg_last_launch
+};
+
+static inline bool ticks_mem_ok(const rcg_handle* h, bool sys_tgt) {
   const bool tgt = (h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0;
-  return tgt == Sys::TGT || (!tgt && Sys::TGT);  // instances exist for the preset's target setting (zeros serve "no target")
+  return tgt == sys_tgt || (!tgt && sys_tgt);  // instances exist for the preset's target setting (zeros serve "no target")
 }
 
+// The caller has checked K, the critic buffers, 1 <= Ncritic - 1 <= kFitMaxRows and no disturbance model.
+template <typename real>
+static int ticks_mem_plan(rcg_handle* h, int DU, bool sys_tgt, bool any_tgt, int32_t T, int32_t K, const void* cand,
+                          TicksMemArgs<real>& M, TicksMemPlan& L) {
+  const rcg_cfg& c = h->cfg;
+  // (a caller's tensor: the streamed decision phase follows the accumulation order of the preset-cost k_actor_dma instances, which
+  // serve the single ticks only under the preset's target setting - whoever compiles, the rule holds there)
+  if ((!any_tgt || cand) && !ticks_mem_ok(h, sys_tgt))
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: no persistent RQL/SQL instance for this observation target");
+  // (structures with >= kFitLanesMinDc weights fit with four lanes per env: the wave's envs must fit its 16 quads)
+  const bool ml = h->dc >= kFitLanesMinDc && c.n_critic - 1 <= 3;
+  if (ml && K < 4)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: K >= 4 with this critic structure (four lanes per env in the fit)");
+  memset(&M, 0, sizeof M);
+  ActorArgs<real>& A = M.A;
+  A.cand = (const real*)cand;  // nullptr: the generated grid
+  A.obs = (const real*)h->f[RCG_FIELD_STATE];
+  A.obs_x = 1;  // the kernel is handed the handle's STATE: y_0 = out(STATE), the identity for the built-ins (actor_plan)
+  A.state_sys = (const real*)h->f[(c.flags & RCG_FLAG_REF_LAG) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
+  A.action_out = (real*)h->f[RCG_FIELD_ACTION];
+  A.best_J = (real*)h->f[RCG_FIELD_BEST_J];
+  A.best_idx = (int32_t*)h->f[RCG_FIELD_BEST_IDX];
+  A.accum = !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
+  A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
+  A.K = K;
+  if (K >= 64) {
+    A.Kp = 64;
+    A.G = 1;
+    A.n_tiles = (K + 63) / 64;
+  } else {
+    int kp = 1;
+    while (kp < K) kp <<= 1;
+    A.Kp = kp;
+    A.G = 64 / kp;
+    A.n_tiles = 1;
+  }
+  A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
+  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+  const size_t row_bytes = (size_t)c.n_actor * DU * sizeof(real);
+  A.vec_ok = (cand && row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
+  const size_t lds = cand ? (size_t)4 * 64 * row_bytes : 0;  // four waves, a 64-row tile each
+  if (lds > (size_t)64 * 1024)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_n: rows of %zu bytes do not fit the persistent kernel's tiles", row_bytes);
+  FitArgs<real>& F = M.F;
+  F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
+  F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
+  F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
+  F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
+  F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
+  F.do_sim = 1;
+  F.do_push = 1;
+  F.state = (const real*)h->f[RCG_FIELD_STATE];
+  F.action = (const real*)h->f[RCG_FIELD_ACTION];
+  F.sim.state = (real*)h->f[RCG_FIELD_STATE];
+  F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
+  F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  F.sim.n_sub = c.substeps_per_tick;
+  M.T = T;
+  M.tick0 = (int)h->tick_count;
+  M.every = c.critic_every_ticks > 1 ? c.critic_every_ticks : 1;
+  const long n_waves = (c.batch + A.G - 1) / A.G;
+  L.cs = c.critic_struct;
+  L.maxm = c.n_critic - 1 <= 3 ? 3 : kFitMaxRows;
+  // (the preset's setting wherever it serves the handle - a built-in system has no other -, else the handle's own)
+  L.tgt = ticks_mem_ok(h, sys_tgt) ? sys_tgt : (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  L.ml = ml;
+  L.stream = cand != nullptr;
+  L.lds = lds;
+  L.grid = dim3((unsigned)((n_waves + 3) / 4));
+  L.block = dim3(256);
+  L.variant = 16 | 1 | (L.tgt ? 2 : 0) | (cand ? 4 : 0);  // variant bit 4: k_ticks_mem
+  return RCG_OK;
+}
+
+// rcg_control_ticks on an RQL / SQL handle: T ticks in one launch (k_ticks_mem), generated candidates or (rcg_control_tick_n)
+// a caller's tensor.
 template <typename Sys>
 int op_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
-  constexpr int DU = Sys::DU;
   const rcg_cfg& c = h->cfg;
-  if (!ticks_mem_ok<Sys>(h)) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: no persistent RQL/SQL instance for this observation target");
-  // (structures with >= 20 weights fit with four lanes per env: the wave's envs must fit its 16 quads)
-  if (dma_dc(c.critic_struct, sys_dy<Sys>(), Sys::DU) >= kFitLanesMinDc && c.n_critic - 1 <= 3 && K < 4)
-    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks: K >= 4 with this critic structure (four lanes per env in the fit)");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     TicksMemArgs<real> M;
-    memset(&M, 0, sizeof M);
-    ActorArgs<real>& A = M.A;
-    A.cand = (const real*)cand;  // nullptr: the generated grid
-    A.obs = (const real*)h->f[RCG_FIELD_STATE];
-    A.state_sys = (const real*)h->f[(c.flags & RCG_FLAG_REF_LAG) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-    A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
-    A.action_out = (real*)h->f[RCG_FIELD_ACTION];
-    A.best_J = (real*)h->f[RCG_FIELD_BEST_J];
-    A.best_idx = (int32_t*)h->f[RCG_FIELD_BEST_IDX];
-    A.accum = !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-    A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
-    A.K = K;
-    if (K >= 64) {
-      A.Kp = 64;
-      A.G = 1;
-      A.n_tiles = (K + 63) / 64;
-    } else {
-      int kp = 1;
-      while (kp < K) kp <<= 1;
-      A.Kp = kp;
-      A.G = 64 / kp;
-      A.n_tiles = 1;
+    TicksMemPlan L;
+    {
+      const int rc = ticks_mem_plan<real>(h, Sys::DU, Sys::TGT, false, T, K, cand, M, L);
+      if (rc) return rc;
     }
-    A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
-    A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
-    const size_t row_bytes = (size_t)c.n_actor * DU * sizeof(real);
-    A.vec_ok = (cand && row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
-    const size_t lds = cand ? (size_t)4 * 64 * row_bytes : 0;  // four waves, a 64-row tile each
-    if (lds > (size_t)64 * 1024)
-      return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_n: rows of %zu bytes do not fit the persistent kernel's tiles", row_bytes);
-    FitArgs<real>& F = M.F;
-    F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
-    F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
-    F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
-    F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
-    F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
-    F.do_sim = 1;
-    F.do_push = 1;
-    F.state = (const real*)h->f[RCG_FIELD_STATE];
-    F.action = (const real*)h->f[RCG_FIELD_ACTION];
-    F.sim.state = (real*)h->f[RCG_FIELD_STATE];
-    F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-    F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
-    F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-    F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
-    F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-    F.sim.n_sub = c.substeps_per_tick;
-    M.T = T;
-    M.tick0 = (int)h->tick_count;
-    M.every = c.critic_every_ticks > 1 ? c.critic_every_ticks : 1;
     const int m = c.n_critic - 1;
-    const long n_waves = (c.batch + A.G - 1) / A.G;
-    const dim3 grid((unsigned)((n_waves + 3) / 4)), block(256);
+    const size_t lds = L.lds;
+    const dim3 grid = L.grid, block = L.block;
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
 #define RCG_TM(CS)                                                                                              \
   do {                                                                                                          \
@@ -1249,7 +1315,7 @@ int op_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
       default: RCG_TM(RCG_CRITIC_QUAD_MIX); break;
     }
 #undef RCG_TM
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, 16 | 1 | (Sys::TGT ? 2 : 0) | (cand ? 4 : 0), A.G);  // variant bit 4: k_ticks_mem
+    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, M.A.G);
     HIPCHK(h, hipGetLastError());
     return (int)RCG_OK;
   });

@@ -102,6 +102,14 @@ __global__ __launch_bounds__(256) void k_ticks(const TicksArgs<real> A, const KP
     else  // k_sim
       env_substeps<Sys, real, TGT>(P, pre, A.n_sub, x, xp, u, st, accum);
     const real* const xs = P.ref_lag ? xp : x;  // rcg_control_tick's state_sys
+    // the tick's observation y_0: the state itself, or (a system with an output map) out(x) as k_out, upd_accum_obj and a
+    // self-driven single tick form it - what the rollouts start from and accum_update is charged at
+    real yo[HasOut<Sys>::value ? sys_dy<Sys>() : 1];
+    const real* y0 = x;
+    if constexpr (HasOut<Sys>::value) {
+      Sys::template out<real, false>(pre, x, yo);
+      y0 = yo;
+    }
     bestJ = inf_r<real>();
     bestI = 0x7fffffff;
     real bestU[DU];
@@ -112,7 +120,7 @@ __global__ __launch_bounds__(256) void k_ticks(const TicksArgs<real> A, const KP
     for (int tl = 0; tl < A.n_tiles; ++tl) {  // k_actor
       if constexpr (!STREAM && !GENERIC && DU == 2 && Sys::SHARED_U1 != 0) {
         if (multi_ok && tl + 4 <= A.n_tiles) {
-          gen_multi_tiles<Sys, real, TGT, 4>(P, pre, N, K, A.grid_g, tl, lane, env_ok, xs, x, bestJ, bestI, bestU);
+          gen_multi_tiles<Sys, real, TGT, 4>(P, pre, N, K, A.grid_g, tl, lane, env_ok, xs, y0, bestJ, bestI, bestU);
           tl += 3;
           continue;
         }
@@ -139,7 +147,7 @@ __global__ __launch_bounds__(256) void k_ticks(const TicksArgs<real> A, const KP
       } else {
         gen_candidate<DU, real>(P, A.grid_g, k, ugen);
       }
-      const real J = rollout_dispatch<Sys, real, GENERIC, TGT, STREAM>(P, pre, N, xs, x, urow, ugen, wget, u0);
+      const real J = rollout_dispatch<Sys, real, GENERIC, TGT, STREAM>(P, pre, N, xs, y0, urow, ugen, wget, u0);
       const real Jc = (J != J) ? inf_r<real>() : J;
       if (valid && (Jc < bestJ || bestI == 0x7fffffff)) {
         bestJ = Jc;
@@ -151,7 +159,7 @@ __global__ __launch_bounds__(256) void k_ticks(const TicksArgs<real> A, const KP
     segment_argmin<DU, real>(seg, bestJ, bestI, bestU);
 #pragma unroll
     for (int c = 0; c < DU; ++c) u[c] = bestU[c];  // receive_action: held until the next tick
-    if (!P.accum_every_substep) accum = accum_update<Sys, TGT, real>(P, x, u, accum);
+    if (!P.accum_every_substep) accum = accum_update<Sys, TGT, real>(P, y0, u, accum);
     steps += 1;
   }
 

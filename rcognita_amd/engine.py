@@ -672,7 +672,8 @@ class Engine:
     def control_tick(self, cand=None, K=None, T=1):
         """One env.control-step for all envs (``T`` > 1: T of them with the same candidates in one native call,
         rcg_control_tick_n - at small batches the Python round trip is longer than the tick and lets the GPU idle and
-        clock down).  ``cand`` on device for
+        clock down).  A system compiled at run time takes the persistent kernels of rcg_control_tick_n only if its policy
+        opts in with ``TICKS``; without it the call loops single ticks, with the same results.  ``cand`` on device for
         the timed path."""
         keep = []
         pc, K = self._cand(cand, keep, K)
@@ -688,7 +689,9 @@ class Engine:
     def control_ticks(self, T, K):
         """``T`` env.control-steps with the generated candidate grid in ONE launch (rcg_control_ticks): bit-identical
         to ``T`` calls of ``control_tick(None, K)``.  MPC with any stage cost, with or without the disturbance model; RQL /
-        SQL whose tick fits k_ticks_mem (rcg.h); other handles are refused (RCG_ERR_UNSUPPORTED) and loop control_tick."""
+        SQL whose tick fits k_ticks_mem (rcg.h); other handles are refused (RCG_ERR_UNSUPPORTED) and loop control_tick.  A
+        system compiled at run time needs ``static constexpr bool TICKS = true;`` in its policy (``_hip_info["has_ticks"]``;
+        RQL / SQL: ``CRITIC`` as well); its instance is compiled on the first call, before anything is enqueued."""
         N.check(N.lib().rcg_control_ticks(self._h, int(T), int(K)), self._h)
 
     def actor_optimize(self, iters=10, obs=None, state_sys=None, u_init=None):

@@ -15,7 +15,8 @@ Same class names, constructor signature and method names as the reference, so a 
 * your own system: instead of overriding ``_state_dyn`` in Python, a subclass sets ``hip_policy`` to the source of a policy
   struct in the shape of the built-ins (rcognita_amd/csrc/rcg_systems.hpp).  The class is compiled for the GPU on its first
   construction (``_native.register_system``) and runs the MPC path (RQL / SQL with ``CRITIC``, the device candidate search
-  with ``SEARCH`` in the policy); INTEGRATION.md, "Your own system".
+  with ``SEARCH``, T ticks per launch with ``TICKS`` in the policy - ``_hip_info["has_ticks"]``); INTEGRATION.md, "Your own
+  system".
 """
 from __future__ import annotations
 

@@ -13,9 +13,12 @@ run-to-run spread is a finding); the same tick of the pendulum with the output m
 The device search (policies with SEARCH): the first-use compile time of the k_actor_search program and the time
 of one rcg_control_tick_search round for the pendulum with and without the output map, f32 and f64, each next to the built-in
 Sys2Tank at the same shape.
+T ticks per launch (policies with TICKS): the first-use compile time of a k_ticks and of a k_ticks_mem program,
+and the rate of rcg_control_ticks(T = 512) against 512 single ticks on the same handle at B = 1024, K = 64, Nactor = 10, f32 and
+f64, interleaved, for the pendulum, the pendulum with the output map and a Sys2Tank copy next to the built-in Sys2Tank.
 GPU box only; no torch.
 
-    python tools/user_system_probe.py [B] [K] [Nactor] [search]      (search: that section alone)
+    python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks]      (search, ticks: that section alone)
 """
 import os
 import sys
@@ -139,8 +142,81 @@ def search_rows():
             e.close()
 
 
+# ---- T ticks per launch on policies with TICKS ----------------------------------------------------------------
+def with_members(src, members):
+    i = src.index("static constexpr int DS")
+    j = src.index("\n", i) + 1
+    return src[:j] + "".join(f"  static constexpr bool {m} = true;\n" for m in members) + src[j:]
+
+
+def ticks_rows(Bt=1024, Kt=64, T=512):
+    tank_src = open(os.path.join(ROOT, "rcognita_amd", "csrc", "rcg_systems.hpp")).read()
+    i = tank_src.index("struct Sys2Tank {")
+    tank_src = tank_src[i:tank_src.index("\n};\n", i) + 4].replace("struct Sys2Tank {", "struct TankTicksProbe {")
+    pend = N.register_system("PendulumTicksProbe", with_members(PENDULUM.replace("PendulumT", "PendulumTicksProbe"), ["TICKS"]), 2, 1, 3)
+    pout = N.register_system("PendulumOutTicksProbe",
+                             with_members(PENDULUM_OUT.replace("PendulumT", "PendulumOutTicksProbe"), ["TICKS", "CRITIC"]), 2, 1, 3)
+    tank = N.register_system("TankTicksProbe", with_members(tank_src, ["TICKS", "CRITIC"]), 2, 1, 5)
+    assert pend["has_ticks"] and pout["has_ticks"] and tank["has_ticks"]
+    rng = np.random.default_rng(2)
+    pb, tb = np.array([[-5.0, 5.0]]), np.array([[0.0, 1.0]])
+    tank_pars, tank_R1, tank_tgt = [18.4, 24.4, 1.3, 1.0, 0.2], np.diag([10.0, 10.0, 1.0]), [0.5, 0.5]
+    cases = (("pendulum (runtime)", pend["sys_id"], [1.3, 9.81, 0.7], np.diag([10.0, 1.0, 0.1]), None, pb, 0.01),
+             ("pendulum with out (runtime)", pout["sys_id"], [1.3, 9.81, 0.7], R1_OUT, None, pb, 0.01),
+             ("Sys2Tank copy (runtime)", tank["sys_id"], tank_pars, tank_R1, tank_tgt, tb, 0.1),
+             ("Sys2Tank (built-in)", N.SYS_2TANK, tank_pars, tank_R1, tank_tgt, tb, 0.1))
+    # first use of a k_ticks_mem program: an RQL handle of the pendulum with out and of the Sys2Tank copy
+    for name, sid, pars, R1, tgt, bnds, dt in cases[1:3]:
+        e = Engine(EngineConfig(sys_id=sid, batch=Bt, dtype="f64", Nactor=NH, mode="RQL", critic_struct="quad-nomix", Ncritic=4,
+                                buffer_size=10, gamma=0.95, pars=pars, ctrl_bnds=bnds, R1=R1, observation_target=tgt, dt_sim=dt,
+                                sampling_time=dt, pred_step_size=2 * dt))
+        e.set_state(rng.uniform(0, 1, (Bt, 2)))
+        t0 = time.perf_counter()
+        e.control_ticks(4, Kt)
+        e.synchronize()
+        ll = e.last_launch()
+        print(f"ticks f64 RQL {name:28s} {ll['kernel']} variant {ll['variant']}: first rcg_control_ticks (compiles the k_ticks_mem "
+              f"program) {time.perf_counter() - t0:.2f} s")
+        e.close()
+    for dtype in ("f32", "f64"):
+        engines = []
+        for name, sid, pars, R1, tgt, bnds, dt in cases:
+            e = Engine(EngineConfig(sys_id=sid, batch=Bt, dtype=dtype, Nactor=NH, pars=pars, ctrl_bnds=bnds, R1=R1,
+                                    observation_target=tgt, dt_sim=dt, sampling_time=dt, pred_step_size=2 * dt))
+            e.set_state(rng.uniform(0, 1, (Bt, 2)))
+            t0 = time.perf_counter()
+            e.control_ticks(4, Kt)
+            e.synchronize()
+            first = time.perf_counter() - t0
+            ll = e.last_launch()
+            e.control_tick(None, K=Kt)  # (the single tick's kernels are part of the core programs)
+            e.synchronize()
+            engines.append((name, e, first, ll, {"one launch": [], "single ticks": []}))
+        for _ in range(5):  # interleaved: both entry points on every handle in turn
+            for name, e, first, ll, rates in engines:
+                for tag in ("one launch", "single ticks"):
+                    t0 = time.perf_counter()
+                    if tag == "one launch":
+                        e.control_ticks(T, Kt)
+                    else:
+                        for _ in range(T):
+                            e.control_tick(None, K=Kt)
+                    e.synchronize()
+                    rates[tag].append(T * Bt / (time.perf_counter() - t0))
+        for name, e, first, ll, rates in engines:
+            a, b = np.median(rates["one launch"]), np.median(rates["single ticks"])
+            print(f"ticks {dtype} {name:28s} {ll['kernel']} variant {ll['variant']}: first rcg_control_ticks {first:.2f} s "
+                  f"({'compiles the k_ticks program' if name.endswith('(runtime)') else 'nothing to compile'}); T = {T} at {Bt} envs x K {Kt} x "
+                  f"Nactor {NH}: one launch {a:.3e} env.control-steps/s ({min(rates['one launch']):.3e} .. {max(rates['one launch']):.3e}), "
+                  f"{T} single ticks {b:.3e} ({min(rates['single ticks']):.3e} .. {max(rates['single ticks']):.3e}), ratio {a / b:.2f}")
+            e.close()
+
+
 if ONLY == "search":
     search_rows()
+    sys.exit(0)
+if ONLY == "ticks":
+    ticks_rows()
     sys.exit(0)
 
 info = N.register_system("PendulumProbe", PENDULUM.replace("PendulumT", "PendulumProbe"), 2, 1, 3)
@@ -259,3 +335,4 @@ for name, e, cand in engines:
     e.close()
 
 search_rows()
+ticks_rows()
