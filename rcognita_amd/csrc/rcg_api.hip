@@ -93,6 +93,24 @@ struct DeviceGuard {
 
 static const int kDims[3][3] = {{5, 2, 2}, {3, 2, 0}, {2, 1, 5}};  // ds, du, np
 
+// The description of system `sys_id`, and for one registered at run time its registry entry (*rtc, else nullptr).  A built-in
+// system has jac_T, observes its state (no output map) and runs every critic mode, k_actor_search, k_ticks and k_ticks_mem
+// instance.  false: no such system.
+static bool system_dims(int sys_id, RtcDims* d, const RtcSystem** rtc = nullptr) {
+  if (rtc) *rtc = nullptr;
+  if (sys_id >= 0 && sys_id <= 2) {
+    *d = RtcDims();
+    d->ds = d->dy = kDims[sys_id][0];
+    d->du = kDims[sys_id][1];
+    d->np = kDims[sys_id][2];
+    d->has_jac = d->has_critic = d->has_search = d->has_ticks = true;
+    return true;
+  }
+  const RtcSystem* S = sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(sys_id, d) : nullptr;
+  if (rtc) *rtc = S;
+  return S != nullptr;
+}
+
 static int dim_critic(int cs, int dy, int du) {
   const int n = dy + du;
   switch (cs) {
@@ -176,11 +194,8 @@ int rcg_version(void) { return RCG_VERSION; }
 const char* rcg_last_error(const rcg_handle* h) { return h ? h->err.c_str() : g_err.c_str(); }
 
 int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32_t* has_jac) {
-  RtcDims d{0, 0, 0, true, 0, false, false};
-  if (sys_id >= 0 && sys_id <= 2)
-    d = RtcDims{kDims[sys_id][0], kDims[sys_id][1], kDims[sys_id][2], true, kDims[sys_id][0], false, false};
-  else if (!(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
-    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_info: bad sys_id %d", sys_id);
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_info: bad sys_id %d", sys_id);
   if (ds) *ds = d.ds;
   if (du) *du = d.du;
   if (np) *np = d.np;
@@ -189,14 +204,32 @@ int rcg_system_info(int32_t sys_id, int32_t* ds, int32_t* du, int32_t* np, int32
 }
 
 int rcg_system_output_info(int32_t sys_id, int32_t* dy, int32_t* has_out, int32_t* has_out_jac) {
-  RtcDims d{0, 0, 0, false, 0, false, false};
-  if (sys_id >= 0 && sys_id <= 2)
-    d.dy = kDims[sys_id][0];  // the built-in systems observe their state
-  else if (!(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
-    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_output_info: bad sys_id %d", sys_id);
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_output_info: bad sys_id %d", sys_id);
   if (dy) *dy = d.dy;
   if (has_out) *has_out = d.has_out ? 1 : 0;
   if (has_out_jac) *has_out_jac = d.has_out_jac ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_critic: bad sys_id %d", sys_id);
+  if (has_critic) *has_critic = d.has_critic ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_search(int32_t sys_id, int32_t* has_search) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_search: bad sys_id %d", sys_id);
+  if (has_search) *has_search = d.has_search ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_ticks: bad sys_id %d", sys_id);
+  if (has_ticks) *has_ticks = d.has_ticks ? 1 : 0;
   return RCG_OK;
 }
 
@@ -213,9 +246,9 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: struct_size %d != sizeof(rcg_cfg) %zu (ABI mismatch)",
                     cfg->struct_size, sizeof(rcg_cfg));
   // a built-in system, or one registered at run time (rcg_rtc.hip: its dimensions come from the registry)
-  RtcDims rd{0, 0, 0, false, 0, false, false};
-  const RtcSystem* rtc = cfg->sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(cfg->sys_id, &rd) : nullptr;
-  if ((cfg->sys_id < 0 || cfg->sys_id > 2) && !rtc)
+  RtcDims rd;
+  const RtcSystem* rtc;
+  if (!system_dims(cfg->sys_id, &rd, &rtc))
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad sys_id %d", cfg->sys_id);
   if (cfg->batch < 1) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: batch must be >= 1");
   if (cfg->dtype != RCG_F32 && cfg->dtype != RCG_F64) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad dtype");
@@ -224,14 +257,14 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad stage_obj_struct");
   if (cfg->critic_struct < 0 || cfg->critic_struct > 3)
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: bad critic_struct");
-  const int ds = rtc ? rd.ds : kDims[cfg->sys_id][0], du = rtc ? rd.du : kDims[cfg->sys_id][1], np = rtc ? rd.np : kDims[cfg->sys_id][2];
+  const int ds = rd.ds, du = rd.du, np = rd.np;
   // (a policy opts in to the critic kernels with `static constexpr bool CRITIC = true`, rcg.h)
   if (rtc && cfg->mode != RCG_MODE_MPC && !rd.has_critic)
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time runs MPC only (no RQL / SQL critic kernels)");
   // the critic's regressor is over [y, u]: its weights must fit w_init / w_min / w_max and the fit kernels' 64-bit variable masks
-  if (dim_critic(cfg->critic_struct, rtc ? rd.dy : ds, du) > RCG_MAX_DC)
+  if (dim_critic(cfg->critic_struct, rd.dy, du) > RCG_MAX_DC)
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: dim_critic %d (dim_output %d, dim_input %d) beyond the limit %d",
-                    dim_critic(cfg->critic_struct, rtc ? rd.dy : ds, du), rtc ? rd.dy : ds, du, RCG_MAX_DC);
+                    dim_critic(cfg->critic_struct, rd.dy, du), rd.dy, du, RCG_MAX_DC);
   if (rtc && (cfg->flags & RCG_FLAG_DISTURB))
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time has no disturbance model");
   // (the reference's horizon is unbounded, controllers.py:965.  Rows of up to RCG_MAX_ROW reals are staged in LDS tiles; longer
@@ -264,7 +297,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->np = np;
   h->rtc_has_out = rtc && rd.has_out;
   h->rtc_has_ticks = rtc && rd.has_ticks;
-  h->dy = rtc ? rd.dy : ds;  // R1 / R2 are (dy + du)^2 and the target has dy entries
+  h->dy = rd.dy;  // R1 / R2 are (dy + du)^2 and the target has dy entries
   h->nchi = h->dy + du;
   h->dc = dim_critic(cfg->critic_struct, h->dy, du);  // the critic's regressor is over [y, u] (controllers.py:1192-1214)
   h->esz = cfg->dtype == RCG_F64 ? 8 : 4;

@@ -268,15 +268,15 @@ extern const SysVTable kVt3WRobot, kVt3WRobotNI, kVt2Tank;
 
 // Systems registered at run time (rcg_register_system, rcg_rtc.hip): the registry entry of `sys_id` and its dimensions, or
 // nullptr for an id nobody registered.  Every such handle shares kVtRtc; the launchers find their system through h->rtc.
-struct RtcDims {
-  int ds, du, np;
-  bool has_jac;      // the policy defines jac_T: k_actor_opt is available
-  int dy;            // dim_output: the policy's DY (default ds)
-  bool has_out;      // the policy defines out (y = out(x)); without it y = x
-  bool has_out_jac;  // ... and out_jac_T, which k_actor_opt needs when there is an output map
-  bool has_critic;   // the policy opts in to the critic kernels (static constexpr bool CRITIC = true): RQL / SQL handles
-  bool has_search;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
-  bool has_ticks;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
+struct RtcDims {  // (`RtcDims d;` is the description of nothing)
+  int ds = 0, du = 0, np = 0;
+  bool has_jac = false;      // the policy defines jac_T: k_actor_opt is available
+  int dy = 0;                // dim_output: the policy's DY (default ds)
+  bool has_out = false;      // the policy defines out (y = out(x)); without it y = x
+  bool has_out_jac = false;  // ... and out_jac_T, which k_actor_opt needs when there is an output map
+  bool has_critic = false;   // the policy opts in to the critic kernels (static constexpr bool CRITIC = true): RQL / SQL handles
+  bool has_search = false;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
+  bool has_ticks = false;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])

@@ -8,28 +8,30 @@
 //                    k_stage_obj, k_sim, k_actor (streamed / generated x generic / diagonal stage cost x target, and the DIRECT
 //                    long-row form), k_actor_opt without LOOP when the policy has jac_T (and out_jac_T if it has out), k_out
 //                    when the policy has an output map `out` (DY = dim_output; every kernel then observes y = out(x));
-//   on first use     k_actor_dma / k_actor_dma_packed at the handle's row length and variant: one small program each, cached;
+//   on first use     one small program per instance, through one routine (lazy_function) and one cache (RtcSystem::lazy) keyed
+//                    by the name expression that selects the instance:
+//                    k_actor_dma / k_actor_dma_packed at the handle's row length and variant (<name>_dma.hip);
 //                    for a policy that opts in with `static constexpr bool CRITIC = true`, the critic program of a handle's
-//                    (element type, critic structure, fit form): k_critic, k_critic_cost and the fit kernel fit_plan picks;
-//                    for a policy that opts in with `static constexpr bool SEARCH = true`, the one k_actor_search instance
-//                    search_plan picks for a handle (element type, generic, target, compile-time horizon): a program each;
+//                    (element type, critic structure, fit form): k_critic, k_critic_cost and the fit kernel fit_plan picks,
+//                    keyed by the fit kernel (<name>_critic.hip);
+//                    for a policy that opts in with `static constexpr bool SEARCH = true`, the k_actor_search instance
+//                    search_plan picks for a handle (<name>_search.hip);
 //                    for a policy that opts in with `static constexpr bool TICKS = true`, the k_ticks instance ticks_plan picks
-//                    (element type, generic, target, streamed) and the k_ticks_mem instance ticks_mem_plan picks (element type,
-//                    critic structure, MAXM, target, four-lane fit, streamed): a program each;
+//                    (<name>_ticks.hip) and the k_ticks_mem instance ticks_mem_plan picks (<name>_ticks_mem.hip);
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan / ticks_plan /
-// ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is not compiled is refused with
-// RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC (rcg_create refuses RQL / SQL for
-// it), the device search of a policy without SEARCH, T ticks per launch of a policy without TICKS, the nominal controllers and
-// rcg_loop_step (rcg_create refuses the disturbance model for these systems).  One mutex guards the registry and every cache, the compiler runs outside it,
-// and a handle keeps the functions it has resolved; nothing is ever unregistered or unloaded (handles point into the registry).
+// ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is
+// not compiled is refused with RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC
+// (rcg_create refuses RQL / SQL for it), the device search of a policy without SEARCH, T ticks per launch of a policy without
+// TICKS, the nominal controllers and rcg_loop_step (rcg_create refuses the disturbance model for these systems).  One mutex
+// guards the registry and every cache, the compiler runs outside it, and a handle keeps the functions it has resolved; nothing
+// is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
 
 #include <cctype>
 #include <map>
 #include <memory>
 #include <mutex>
-#include <tuple>
 
 #include "rcg_rtc_headers.inc"  // kRtcHeaderCount, kRtcHeaderNames, kRtcHeaderTexts (generated under build/)
 #include "rcg_sysops.hpp"
@@ -41,8 +43,9 @@ namespace {
 struct RtcProgram {
   std::string code;                                  // code object for gfx950
   std::map<std::string, std::string> lowered;        // name expression -> lowered name
-  std::map<int, hipModule_t> module;                 // device -> loaded code object
-  std::map<std::pair<int, std::string>, hipFunction_t> fn;
+  // (filled as devices first launch from the program, under g_mu: not part of what a registered system is)
+  mutable std::map<int, hipModule_t> module;         // device -> loaded code object
+  mutable std::map<std::pair<int, std::string>, hipFunction_t> fn;
 };
 
 }  // namespace
@@ -54,12 +57,9 @@ struct RtcSystem {
   bool tgt;                 // the policy's TGT (default false): which k_actor_dma instance serves a handle with a target
   unsigned zw;              // the policy's ZW_PRESET (default 0): the zero-weight instance of k_actor_dma's DMA_MPC_G1 (float64)
   RtcProgram core[2];       // [0] float, [1] double
-  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> dma;  // (f64, packed, R, variant | 256: zero-weight instance)
-  std::map<std::tuple<int, int, int>, std::unique_ptr<RtcProgram>> critic;    // (f64, critic structure, FIT_FORM_*)
-  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> search;  // (f64, generic, tgt, nc): k_actor_search
-  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> ticks;   // (f64, generic, tgt, stream): k_ticks
-  // (f64, critic structure, MAXM, tgt | 2 ml | 4 stream): k_ticks_mem
-  std::map<std::tuple<int, int, int, int>, std::unique_ptr<RtcProgram>> ticks_mem;
+  // the programs compiled on first use (lazy_function), by the name expression that defines each: the instance itself, or the
+  // fit kernel of a critic program
+  std::map<std::string, std::unique_ptr<RtcProgram>> lazy;
   std::vector<std::string> compiled;  // "<program>\t<name expression>" of everything compiled so far (rcg_system_programs)
 };
 
@@ -84,9 +84,12 @@ bool is_identifier(const char* s) {
   return strlen(s) < 128;
 }
 
-// The generated unit: the kernel headers, the policy (its own file name and line numbers in hipRTC's log), the adapter that
-// supplies the optional members and the checks of the declared dimensions.
-std::string unit_source(const RtcSystem& S, bool critic = false, bool search = false, bool ticks = false) {
+// The generated unit: the kernel headers of its flavour (Core: the probe, the core programs and the k_actor_dma instances), the
+// policy (its own file name and line numbers in hipRTC's log), the adapter that supplies the optional members and the checks of
+// the declared dimensions.
+enum class Unit { Core, Critic, Search, Ticks };
+std::string unit_source(const RtcSystem& S, Unit unit) {
+  const bool critic = unit == Unit::Critic, search = unit == Unit::Search, ticks = unit == Unit::Ticks;
   char dims[1536];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
@@ -282,7 +285,7 @@ std::vector<std::string> core_exprs(const RtcDims& d) {
 }
 
 // the function `expr` of program `P` on the handle's device (the caller holds g_mu)
-int function(rcg_handle* h, RtcProgram& P, const std::string& expr, hipFunction_t* fn) {
+int function(rcg_handle* h, const RtcProgram& P, const std::string& expr, hipFunction_t* fn) {
   const int dev = h->cfg.device;
   auto it = P.fn.find({dev, expr});
   if (it != P.fn.end()) {
@@ -313,196 +316,94 @@ int core_function(rcg_handle* h, const std::string& expr, hipFunction_t* fn) {
     return RCG_OK;
   }
   std::lock_guard<std::mutex> lock(g_mu);
-  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  const int rc = function(h, S.core[sizeof(real) == 8 ? 1 : 0], expr, fn);
+  const int rc = function(h, h->rtc->core[sizeof(real) == 8 ? 1 : 0], expr, fn);
   if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
   return rc;
 }
 
-// k_actor_dma / k_actor_dma_packed at the handle's row length: compiled the first time a handle of this (system, element type)
-// asks for it - outside the lock, so that launches of other handles do not wait for the compiler - then cached
-template <typename real>
-int dma_function(rcg_handle* h, bool packed, int R, int variant, unsigned zw, hipFunction_t* fn) {
-  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  const std::string expr = expr_dma<real>(packed, R, variant, S.tgt, zw);
+// A program compiled on first use: the unit of flavour `unit` with the name expressions `exprs`, as <name>_<kind>.hip.  The last
+// expression defines the program and is its key in RtcSystem::lazy, so the instance that is selected and the entry that is
+// cached cannot differ.  *fn is the function of exprs[want].  The program is compiled the first time a handle asks for it -
+// outside the lock, so that launches of other handles do not wait for the compiler - and published under it unless another
+// thread has published it meanwhile (this one's is then dropped); rcg_system_programs lists it from then on.  A compile error is
+// compile()'s code - RCG_ERR_BAD_ARG when the source is at fault (a member of the policy the program instantiates for the first
+// time) - with hipRTC's log in the handle's error text.
+int lazy_function(rcg_handle* h, Unit unit, const char* kind, const std::vector<std::string>& exprs, size_t want,
+                  hipFunction_t* fn) {
+  const std::string& expr = exprs[want];
   auto hit = h->rtc_fn.find(expr);
   if (hit != h->rtc_fn.end()) {
     *fn = hit->second;
     return RCG_OK;
   }
-  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, packed ? 1 : 0, R, variant | (zw ? 256 : 0));
+  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
+  const std::string& key = exprs.back();
   bool have;
   {
     std::lock_guard<std::mutex> lock(g_mu);
-    have = S.dma.count(key) != 0;
+    have = S.lazy.count(key) != 0;
   }
+  const std::string file = S.name + "_" + kind + ".hip";
   std::unique_ptr<RtcProgram> P;
   if (!have) {
     P.reset(new RtcProgram);
     std::string log;
-    const int rc = compile(unit_source(S), S.name + "_dma.hip", {expr}, P.get(), &log);
+    const int rc = compile(unit_source(S, unit), file, exprs, P.get(), &log);
     if (rc) {
-      h->err = "runtime system " + S.name + ": compiling " + expr + ": " + log;
-      return RCG_ERR_HIP;
+      const std::string what = exprs.size() == 1 ? key : std::string("the ") + kind + " program (" + key + ")";
+      h->err = "runtime system " + S.name + ": compiling " + what + ": " + log;
+      return rc;
     }
   }
   std::lock_guard<std::mutex> lock(g_mu);
-  auto it = S.dma.find(key);
-  if (it == S.dma.end()) {  // (else another thread has published it meanwhile)
-    it = S.dma.emplace(key, std::move(P)).first;
-    S.compiled.push_back(S.name + "_dma.hip\t" + expr);
+  auto it = S.lazy.find(key);
+  if (it == S.lazy.end()) {  // (else another thread has published it meanwhile)
+    it = S.lazy.emplace(key, std::move(P)).first;
+    for (const auto& e : exprs) S.compiled.push_back(file + "\t" + e);
   }
   const int rc = function(h, *it->second, expr, fn);
   if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
   return rc;
+}
+
+// The k_actor_dma and critic programs answer a compile error with RCG_ERR_HIP, the later ones (search, ticks) with compile()'s
+// RCG_ERR_BAD_ARG.  Kept on purpose: the codes are part of the library's behaviour, whichever of the two is the better one.
+int compile_error_is_hip(int rc) { return rc == RCG_ERR_BAD_ARG ? RCG_ERR_HIP : rc; }
+
+// k_actor_dma / k_actor_dma_packed at the handle's row length
+template <typename real>
+int dma_function(rcg_handle* h, bool packed, int R, int variant, unsigned zw, hipFunction_t* fn) {
+  const int rc = lazy_function(h, Unit::Core, "dma", {expr_dma<real>(packed, R, variant, h->rtc->tgt, zw)}, 0, fn);
+  return compile_error_is_hip(rc);
 }
 
 // The critic program of the handle's (element type, critic structure) and of fit form `form`: k_critic, k_critic_cost and that
-// form's fit kernel - compiled the first time a handle asks for it, as the k_actor_dma instances are, then cached.  Any of the
-// three out-pointers may be null.
+// form's fit kernel; `want`: which of the three
+enum { CRITIC_VALUE = 0, CRITIC_COST = 1, CRITIC_FIT = 2 };
 template <typename real>
-int critic_functions(rcg_handle* h, int form, hipFunction_t* f_critic, hipFunction_t* f_cost, hipFunction_t* f_fit) {
-  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  if (!S.dims.has_critic) return RCG_ERR_UNSUPPORTED;  // (the callers refuse by name first)
-  const int cs = h->cfg.critic_struct;
-  const std::string e[3] = {expr_critic<real>(), expr_critic_cost<real>(), expr_fit<real>(cs, form)};
-  hipFunction_t* const out[3] = {f_critic, f_cost, f_fit};
-  bool all = true;
-  for (int i = 0; i < 3; ++i) {
-    if (!out[i]) continue;
-    auto hit = h->rtc_fn.find(e[i]);
-    if (hit != h->rtc_fn.end())
-      *out[i] = hit->second;
-    else
-      all = false;
-  }
-  if (all) return RCG_OK;
-  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, cs, form);
-  bool have;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    have = S.critic.count(key) != 0;
-  }
-  const std::string file = S.name + "_critic.hip";
-  std::unique_ptr<RtcProgram> P;
-  if (!have) {
-    P.reset(new RtcProgram);
-    std::string log;
-    const int rc = compile(unit_source(S, true), file, {e[0], e[1], e[2]}, P.get(), &log);
-    if (rc) {
-      h->err = "runtime system " + S.name + ": compiling the critic program (" + e[2] + "): " + log;
-      return RCG_ERR_HIP;
-    }
-  }
-  std::lock_guard<std::mutex> lock(g_mu);
-  auto it = S.critic.find(key);
-  if (it == S.critic.end()) {
-    it = S.critic.emplace(key, std::move(P)).first;
-    for (const auto& x : e) S.compiled.push_back(file + "\t" + x);
-  }
-  for (int i = 0; i < 3; ++i) {
-    if (!out[i]) continue;
-    const int rc = function(h, *it->second, e[i], out[i]);
-    if (rc) return rc;
-    h->rtc_fn[e[i]] = *out[i];
-  }
-  return RCG_OK;
+int critic_function(rcg_handle* h, int form, int want, hipFunction_t* fn) {
+  if (!h->rtc->dims.has_critic) return RCG_ERR_UNSUPPORTED;  // (the callers refuse by name first)
+  const std::vector<std::string> exprs{expr_critic<real>(), expr_critic_cost<real>(),
+                                       expr_fit<real>(h->cfg.critic_struct, form)};
+  return compile_error_is_hip(lazy_function(h, Unit::Critic, "critic", exprs, want, fn));
+}
+// ... of the form the handle's critic update takes (fit_plan): what a tick resolves before it enqueues anything
+int critic_fit_function(rcg_handle* h, hipFunction_t* fn) {
+  return by_dtype(h, [&](auto r) {
+    return critic_function<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), CRITIC_FIT, fn);
+  });
 }
 
-// The k_actor_search instance of a plan: a program of its own, compiled the first time a handle of this (system, element type,
-// generic, tgt, nc) asks for it, as the k_actor_dma instances are, then cached.  A compile error is RCG_ERR_BAD_ARG with hipRTC's
-// log (the policy's source is at fault: a member the search instantiates for the first time).  dma_function and
-// critic_functions answer a compile error with RCG_ERR_HIP instead; they predate this and keep their code.
+// the k_actor_search instance of a plan (search_plan gives nc > 0 only where tgt == Sys::TGT)
 template <typename real>
 int search_function(rcg_handle* h, const SearchPlan& L, hipFunction_t* fn) {
-  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  const bool tgt = L.tgt;  // (search_plan gives nc > 0 only where tgt == Sys::TGT)
-  const std::string expr = expr_search<real>(L.generic, tgt, L.nc);
-  auto hit = h->rtc_fn.find(expr);
-  if (hit != h->rtc_fn.end()) {
-    *fn = hit->second;
-    return RCG_OK;
-  }
-  const auto key = std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.generic ? 1 : 0, tgt ? 1 : 0, L.nc);
-  bool have;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    have = S.search.count(key) != 0;
-  }
-  const std::string file = S.name + "_search.hip";
-  std::unique_ptr<RtcProgram> P;
-  if (!have) {
-    P.reset(new RtcProgram);
-    std::string log;
-    const int rc = compile(unit_source(S, false, true), file, {expr}, P.get(), &log);
-    if (rc) {
-      h->err = "runtime system " + S.name + ": compiling " + expr + ": " + log;
-      return rc;
-    }
-  }
-  std::lock_guard<std::mutex> lock(g_mu);
-  auto it = S.search.find(key);
-  if (it == S.search.end()) {  // (else another thread has published it meanwhile)
-    it = S.search.emplace(key, std::move(P)).first;
-    S.compiled.push_back(file + "\t" + expr);
-  }
-  const int rc = function(h, *it->second, expr, fn);
-  if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
-  return rc;
+  return lazy_function(h, Unit::Search, "search", {expr_search<real>(L.generic, L.tgt, L.nc)}, 0, fn);
 }
 
-// The k_ticks / k_ticks_mem instance of a plan: a program of its own, compiled the first time a handle of this system asks for the
-// key, as the k_actor_search instances are, then cached.  A compile error is RCG_ERR_BAD_ARG with hipRTC's log.
-int ticks_function(rcg_handle* h, bool mem, const std::tuple<int, int, int, int>& key, const std::string& expr, hipFunction_t* fn) {
-  RtcSystem& S = *const_cast<RtcSystem*>(h->rtc);
-  auto hit = h->rtc_fn.find(expr);
-  if (hit != h->rtc_fn.end()) {
-    *fn = hit->second;
-    return RCG_OK;
-  }
-  auto& cache = mem ? S.ticks_mem : S.ticks;
-  bool have;
-  {
-    std::lock_guard<std::mutex> lock(g_mu);
-    have = cache.count(key) != 0;
-  }
-  const std::string file = S.name + (mem ? "_ticks_mem.hip" : "_ticks.hip");
-  std::unique_ptr<RtcProgram> P;
-  if (!have) {
-    P.reset(new RtcProgram);
-    std::string log;
-    const int rc = compile(unit_source(S, false, false, true), file, {expr}, P.get(), &log);
-    if (rc) {
-      h->err = "runtime system " + S.name + ": compiling " + expr + ": " + log;
-      return rc;
-    }
-  }
-  std::lock_guard<std::mutex> lock(g_mu);
-  auto it = cache.find(key);
-  if (it == cache.end()) {  // (else another thread has published it meanwhile)
-    it = cache.emplace(key, std::move(P)).first;
-    S.compiled.push_back(file + "\t" + expr);
-  }
-  const int rc = function(h, *it->second, expr, fn);
-  if (rc == RCG_OK) h->rtc_fn[expr] = *fn;
-  return rc;
-}
-
-int refuse_ticks(rcg_handle* h, const char* who) {
+// a member of the table that the policy did not opt in to with `member` (CRITIC, SEARCH, TICKS)
+int refuse_opt_in(rcg_handle* h, const char* who, const char* member) {
   return rcg_fail(h, RCG_ERR_UNSUPPORTED,
-                  "%s: not available for a system registered at run time whose policy does not opt in with TICKS (%s)", who,
-                  h->rtc ? h->rtc->name.c_str() : "?");
-}
-
-int refuse_search(rcg_handle* h, const char* who) {
-  return rcg_fail(h, RCG_ERR_UNSUPPORTED,
-                  "%s: not available for a system registered at run time whose policy does not opt in with SEARCH (%s)", who,
-                  h->rtc ? h->rtc->name.c_str() : "?");
-}
-
-int refuse_critic(rcg_handle* h, const char* who) {
-  return rcg_fail(h, RCG_ERR_UNSUPPORTED,
-                  "%s: not available for a system registered at run time whose policy does not opt in with CRITIC (%s)", who,
+                  "%s: not available for a system registered at run time whose policy does not opt in with %s (%s)", who, member,
                   h->rtc ? h->rtc->name.c_str() : "?");
 }
 
@@ -707,7 +608,7 @@ int rtc_critic(rcg_handle* h, const void* obs, const void* act, const void* w, v
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     hipFunction_t f;
-    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), &f, nullptr, nullptr);
+    int rc = critic_function<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), CRITIC_VALUE, &f);
     if (rc) return rc;
     const real* o = (const real*)obs;
     const real* a = (const real*)act;
@@ -725,7 +626,7 @@ int rtc_critic_cost(rcg_handle* h, const void* w, void* Jc) {
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     hipFunction_t f;
-    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, &f, nullptr);
+    int rc = critic_function<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), CRITIC_COST, &f);
     if (rc) return rc;
     const real* ww = w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC];
     const real* wp = (const real*)h->f[RCG_FIELD_W_PREV];
@@ -745,7 +646,7 @@ int rtc_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_
     // the form, the grid and the variant word of op_critic_update; the function is resolved before the scratch tensor of
     // k_critic_fit_gen is sized and before anything is enqueued
     hipFunction_t f;
-    int rc = critic_functions<real>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
+    int rc = critic_fit_function(h, &f);
     if (rc) return rc;
     ProfScope prof_scope(h, RCG_KERNEL_CRITIC);
     FitArgs<real> F;
@@ -768,7 +669,7 @@ int rtc_nominal(rcg_handle* h, const void*, void*, void*, void*, int32_t, double
 // except the shell written for one built-in system (k_ticks_pk).  The instance is resolved - and compiled, the first time -
 // before anything is enqueued.
 int rtc_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
-  if (!h->rtc->dims.has_ticks) return refuse_ticks(h, "rcg_control_ticks");
+  if (!h->rtc->dims.has_ticks) return refuse_opt_in(h, "rcg_control_ticks", "TICKS");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const RtcSystem& S = *h->rtc;
@@ -777,8 +678,7 @@ int rtc_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     int rc = ticks_plan<real>(h, S.dims.du, T, K, cand, A, L);
     if (rc) return rc;
     hipFunction_t f;
-    rc = ticks_function(h, false, std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.generic ? 1 : 0, L.tgt ? 1 : 0, L.stream ? 1 : 0),
-                        expr_ticks<real>(L), &f);
+    rc = lazy_function(h, Unit::Ticks, "ticks", {expr_ticks<real>(L)}, 0, &f);
     if (rc) return rc;
     KParams<real> P = params<real>(h);
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
@@ -791,8 +691,8 @@ int rtc_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
   });
 }
 int rtc_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
-  if (!h->rtc->dims.has_ticks) return refuse_ticks(h, "rcg_control_ticks");
-  if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_ticks");
+  if (!h->rtc->dims.has_ticks) return refuse_opt_in(h, "rcg_control_ticks", "TICKS");
+  if (!h->rtc->dims.has_critic) return refuse_opt_in(h, "rcg_control_ticks", "CRITIC");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const RtcSystem& S = *h->rtc;
@@ -801,9 +701,7 @@ int rtc_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     int rc = ticks_mem_plan<real>(h, S.dims.du, S.tgt, true, T, K, cand, M, L);
     if (rc) return rc;
     hipFunction_t f;
-    rc = ticks_function(h, true,
-                        std::make_tuple(sizeof(real) == 8 ? 1 : 0, L.cs, L.maxm, (L.tgt ? 1 : 0) | (L.ml ? 2 : 0) | (L.stream ? 4 : 0)),
-                        expr_ticks_mem<real>(L), &f);
+    rc = lazy_function(h, Unit::Ticks, "ticks_mem", {expr_ticks_mem<real>(L)}, 0, &f);
     if (rc) return rc;
     KParams<double> P64 = h->p64;
     KParams<real> P = params<real>(h);
@@ -821,7 +719,7 @@ int rtc_rhs_full(rcg_handle* h, const void*, const void*, const void*, const voi
 // compiled, the first time - before anything is enqueued.
 int rtc_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const void* obs, const void* state_sys, const void* centre,
                int shift, void* u_best, void* action, void* best_J, int32_t* best_idx, bool tick, bool sim_first) {
-  if (!h->rtc->dims.has_search) return refuse_search(h, "rcg_actor_search");
+  if (!h->rtc->dims.has_search) return refuse_opt_in(h, "rcg_actor_search", "SEARCH");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const RtcSystem& S = *h->rtc;
@@ -857,7 +755,7 @@ int probe(RtcSystem& S, std::string* log) {
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
                         ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET>";
   RtcProgram P;
-  const int rc = compile(unit_source(S), S.name + "_probe.hip", {e}, &P, log);
+  const int rc = compile(unit_source(S, Unit::Core), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
   long v[9];
@@ -917,11 +815,9 @@ int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
 // rcg_control_tick, RQL / SQL: every instance the tick launches - the critic program's fit kernel and the decision kernel of this
 // (cand, K) - resolved, and compiled on first use, before the tick enqueues anything
 int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K) {
-  if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_tick");
-  int rc = by_dtype(h, [&](auto r) {
-    hipFunction_t f;
-    return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
-  });
+  if (!h->rtc->dims.has_critic) return refuse_opt_in(h, "rcg_control_tick", "CRITIC");
+  hipFunction_t fit;
+  int rc = critic_fit_function(h, &fit);
   if (rc) return rc;
   return by_dtype(h, [&](auto r) {  // the tick's own plan (the arguments rcg_control_tick hands the launcher), and its instance
     using real = decltype(r);
@@ -940,13 +836,11 @@ int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K) {
 // the tick's own plan and, RQL / SQL, the critic program's fit kernel - resolved, and compiled on first use, before the tick
 // enqueues anything: a compile failure leaves every field of the handle as it was
 int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t warm) {
-  if (!h->rtc->dims.has_search) return refuse_search(h, "rcg_control_tick_search");
+  if (!h->rtc->dims.has_search) return refuse_opt_in(h, "rcg_control_tick_search", "SEARCH");
   if (h->cfg.mode != RCG_MODE_MPC) {
-    if (!h->rtc->dims.has_critic) return refuse_critic(h, "rcg_control_tick_search");
-    const int rc = by_dtype(h, [&](auto r) {
-      hipFunction_t f;
-      return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
-    });
+    if (!h->rtc->dims.has_critic) return refuse_opt_in(h, "rcg_control_tick_search", "CRITIC");
+    hipFunction_t fit;
+    const int rc = critic_fit_function(h, &fit);
     if (rc) return rc;
   }
   return by_dtype(h, [&](auto r) {
@@ -967,14 +861,12 @@ int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t wa
 // (the optimiser's instances belong to the core programs compiled at registration)
 int rtc_prepare_tick_opt(rcg_handle* h) {
   const RtcDims& d = h->rtc->dims;
-  if (!d.has_critic) return refuse_critic(h, "rcg_control_tick_opt");
+  if (!d.has_critic) return refuse_opt_in(h, "rcg_control_tick_opt", "CRITIC");
   if (!d.has_jac || (d.has_out && !d.has_out_jac))
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_opt: the policy %s defines no jac_T%s (the optimiser's adjoint sweep)",
                     h->rtc->name.c_str(), d.has_out ? " / out_jac_T" : "");
-  return by_dtype(h, [&](auto r) {
-    hipFunction_t f;
-    return critic_functions<decltype(r)>(h, fit_form_of(h->cfg.n_critic - 1, h->dc, false), nullptr, nullptr, &f);
-  });
+  hipFunction_t fit;
+  return critic_fit_function(h, &fit);
 }
 
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims) {
@@ -1019,7 +911,10 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   std::unique_ptr<RtcSystem> S(new RtcSystem);
   S->name = name;
   S->src = policy_src;
-  S->dims = RtcDims{ds, du, np, false, ds, false, false, false, false, false};
+  S->dims.ds = ds;
+  S->dims.du = du;
+  S->dims.np = np;
+  S->dims.dy = ds;  // (the probe reads the policy's own DY and its optional members)
   S->tgt = false;
   std::string log;
   rc = probe(*S, &log);
@@ -1027,8 +922,9 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   // refused by the adapter's static_assert above, with hipRTC's log)
   if (rc == RCG_OK && (S->dims.dy < 1 || S->dims.dy > RCG_MAX_DS))
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::DY = %d beyond 1 .. %d", name, S->dims.dy, RCG_MAX_DS);
-  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f32.hip", core_exprs<float>(S->dims), &S->core[0], &log);
-  if (rc == RCG_OK) rc = compile(unit_source(*S), S->name + "_f64.hip", core_exprs<double>(S->dims), &S->core[1], &log);
+  const std::string unit = unit_source(*S, Unit::Core);
+  if (rc == RCG_OK) rc = compile(unit, S->name + "_f32.hip", core_exprs<float>(S->dims), &S->core[0], &log);
+  if (rc == RCG_OK) rc = compile(unit, S->name + "_f64.hip", core_exprs<double>(S->dims), &S->core[1], &log);
   if (rc) {
     rcg_set_thread_error(std::string("rcg_register_system: ") + name + ": " + log);
     return rc;
@@ -1040,30 +936,6 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   S->id = RCG_SYS_USER_BASE + (int)g_sys.size();
   *sys_id = S->id;
   g_sys.push_back(std::move(S));
-  return RCG_OK;
-}
-
-int rcg_system_has_critic(int32_t sys_id, int32_t* has_critic) {
-  RtcDims d{0, 0, 0, false, 0, false, false, true};  // (the built-in systems run every critic mode)
-  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
-    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_critic: bad sys_id %d", sys_id);
-  if (has_critic) *has_critic = d.has_critic ? 1 : 0;
-  return RCG_OK;
-}
-
-int rcg_system_has_search(int32_t sys_id, int32_t* has_search) {
-  RtcDims d{0, 0, 0, false, 0, false, false, true, true};  // (the built-in systems have every k_actor_search instance)
-  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
-    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_search: bad sys_id %d", sys_id);
-  if (has_search) *has_search = d.has_search ? 1 : 0;
-  return RCG_OK;
-}
-
-int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks) {
-  RtcDims d{0, 0, 0, false, 0, false, false, true, true, true};  // (the built-in systems have every k_ticks / k_ticks_mem instance)
-  if (!(sys_id >= 0 && sys_id <= 2) && !(sys_id >= RCG_SYS_USER_BASE && rtc_lookup(sys_id, &d)))
-    return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_ticks: bad sys_id %d", sys_id);
-  if (has_ticks) *has_ticks = d.has_ticks ? 1 : 0;
   return RCG_OK;
 }
 
