@@ -436,7 +436,7 @@ int rtc_rhs(rcg_handle* h, const void* state, const void* action, void* dstate, 
     const real* ac = (const real*)action;
     real* ds = (real*)dstate;
     real* cl = (real*)clipped;
-    const real* pe = (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
+    const real* pe = pars_env_of<real>(h, n);
     long nn = n;
     int ci = clip;
     KParams<real> P = params<real>(h);
@@ -509,13 +509,7 @@ int actor(rcg_handle* h, const char* who, const void* cand, int K, const void* o
   ActorPlan L;
   int rc = actor_plan<real>(h, who, S.dims.ds, S.dims.du, S.tgt, cand, K, obs, state_sys, w, J, action, best_J, best_idx, tick,
                             sim_first, A, L);
-  if (rc) return rc;
-  if (h->probe == 1) {
-    h->probe = (L.dma_ok && !L.pack_ok) ? 3 : 2;
-    return RCG_OK;
-  }
-  if (h->sub_hi > 0 && !(L.dma_ok && !L.pack_ok))
-    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: a split tick needs the k_actor_dma shape", who);
+  if (rc || actor_plan_answers(h, who, L, rc)) return rc;
   ActorPick pick;
   rc = resolve_actor_instance<real>(h, A, L, cand != nullptr, &pick);
   if (rc) return rc;
@@ -548,9 +542,7 @@ int actor(rcg_handle* h, const char* who, const void* cand, int K, const void* o
   }
   void* args[] = {&A, &P};
   rc = launch(h, f, dim3(L.blocks), dim3(64 * L.wpb), L.long_row ? 0 : L.lds, args);
-  if (rc == RCG_OK)
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR,
-                L.long_row ? (1 | (L.tgt ? 2 : 0) | 4 | 16) : ((L.generic ? 1 : 0) | (L.tgt ? 2 : 0) | (cand ? 4 : 0)), A.G);
+  if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, L.word, A.G);
   return rc;
 }
 
@@ -573,31 +565,24 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
   if (h->loop_io.on) return refuse(h, "rcg_loop_step");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
-    const rcg_cfg& c = h->cfg;
     OptArgs<real> A;
-    int wpb;
-    size_t lds;
-    int rc = opt_plan<real>(h, h->du, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, wpb, lds);
+    OptPlan L;
+    int rc = opt_plan<real>(h, h->du, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, L);
     if (rc) return rc;
     KParams<real> P = params<real>(h);
-    // (RQL / SQL run on the generic instance, as they do for the built-in systems; its critic terms are over [y, u])
-    const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
-    const bool tgt = c.flags & RCG_FLAG_HAS_TARGET;
-    const bool pairs = A.memory > 0;
     hipFunction_t f;
-    rc = core_function<real>(h, expr_opt<real>(tgt, generic, pairs), &f);
+    rc = core_function<real>(h, expr_opt<real>(L.tgt, L.generic, L.pairs), &f);
     if (rc) return rc;
     if (tick && sim_first) {
-      rc = sim_step<real>(h, c.substeps_per_tick);
+      rc = sim_step<real>(h, h->cfg.substeps_per_tick);
       if (rc) return rc;
     }
     // (beyond 64 KB of dynamic LDS the built-in launcher calls hipFuncSetAttribute, which has no module-function form and
     // admits any size up to the CU's 160 KB on this platform: the module launch takes the size as it is)
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
     void* args[] = {&A, &P};
-    rc = launch(h, f, dim3(blocks_for(c.batch, wpb * OPT_G)), dim3(64 * wpb), lds, args);
-    if (rc == RCG_OK)
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, (generic ? 1 : 0) | (tgt ? 2 : 0) | (pairs ? 4 : 0), OPT_G);
+    rc = launch(h, f, L.grid, L.block, L.lds, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, L.variant, OPT_G);
     return rc;
   });
 }
@@ -804,7 +789,7 @@ int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
     if (rc) return rc;
     const real* st = (const real*)state;
     real* y = (real*)obs;
-    const real* pe = (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
+    const real* pe = pars_env_of<real>(h, n);
     long nn = n;
     KParams<real> P = params<real>(h);
     void* args[] = {&st, &y, &pe, &nn, &P};

@@ -27,16 +27,52 @@ static int by_dtype(rcg_handle* h, F&& f) {
   return h->cfg.dtype == RCG_F64 ? f(double{}) : f(float{});
 }
 
+// the launch epilogue of every launcher: [what rcg_last_launch reports] -> the launch's own error -> RCG_OK
+static inline int launch_done(rcg_handle* h) {
+  HIPCHK(h, hipGetLastError());
+  return RCG_OK;
+}
+static inline int launch_done(rcg_handle* h, int kind, int kernel_id, int variant, int envs_per_wave) {
+  note_launch(h, kind, kernel_id, variant, envs_per_wave);
+  return launch_done(h);
+}
+
+// f(std::bool_constant...) for runtime bools: the one way from runtime values to a kernel instance.  A launcher whose set of
+// instances is no full product keeps an explicit branch around it.
+template <typename F>
+static auto with_bools(F&& f) {
+  return f();
+}
+template <typename F, typename... Bs>
+static auto with_bools(F&& f, bool b, Bs... rest) {
+  if (b) return with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...);
+  return with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+// f(std::integral_constant<int, CS>) for the handle's critic structure
+template <typename F>
+static auto with_critic(int cs, F&& f) {
+  switch (cs) {
+    case RCG_CRITIC_QUAD_LIN: return f(std::integral_constant<int, RCG_CRITIC_QUAD_LIN>{});
+    case RCG_CRITIC_QUADRATIC: return f(std::integral_constant<int, RCG_CRITIC_QUADRATIC>{});
+    case RCG_CRITIC_QUAD_NOMIX: return f(std::integral_constant<int, RCG_CRITIC_QUAD_NOMIX>{});
+    default: return f(std::integral_constant<int, RCG_CRITIC_QUAD_MIX>{});
+  }
+}
+
+// the per-env parameters of an operator on n points: only when the points are the handle's envs
+template <typename real>
+static const real* pars_env_of(const rcg_handle* h, long n) {
+  return (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
+}
+
 template <typename Sys>
 static int op_rhs(rcg_handle* h, const void* state, const void* action, void* dstate, void* clipped, int32_t n,
                   int32_t clip) {
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
-    const real* pe = (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
     hipLaunchKernelGGL((k_rhs<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, h->stream, (const real*)state,
-                       (const real*)action, (real*)dstate, (real*)clipped, pe, (long)n, (int)clip, params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+                       (const real*)action, (real*)dstate, (real*)clipped, pars_env_of<real>(h, n), (long)n, (int)clip, params<real>(h));
+    return launch_done(h);
   });
 }
 
@@ -58,12 +94,10 @@ static int op_rhs_full(rcg_handle* h, const void* state, const void* disturb, co
                        void* dstate, void* ddisturb, void* clipped, int32_t n, int32_t clip) {
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
-    const real* pe = (h->f[RCG_FIELD_PARS] && n == h->cfg.batch) ? (const real*)h->f[RCG_FIELD_PARS] : nullptr;
     hipLaunchKernelGGL((k_rhs_full<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, h->stream, (const real*)state,
                        (const real*)disturb, (const real*)action, (const real*)xi, (real*)dstate, (real*)ddisturb,
-                       (real*)clipped, pe, (long)n, (int)clip, disturb_pars(h), params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+                       (real*)clipped, pars_env_of<real>(h, n), (long)n, (int)clip, disturb_pars(h), params<real>(h));
+    return launch_done(h);
   });
 }
 
@@ -73,9 +107,24 @@ static int op_stage_obj(rcg_handle* h, const void* obs, const void* act, void* o
     using real = decltype(r);
     hipLaunchKernelGGL((k_stage_obj<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, h->stream, (const real*)obs,
                        (const real*)act, (real*)out, (long)n, params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    return launch_done(h);
   });
+}
+
+// the env step's arguments: the handle's own fields.  The only code that writes a SimArgs (k_sim, k_sim_v, k_sim_dist, the
+// env step inside k_loop, the critic fit, k_ticks_mem and k_actor_dma_packed; rcg_rtc.hip)
+template <typename real>
+static SimArgs<real> sim_args(const rcg_handle* h, int32_t n_substeps) {
+  SimArgs<real> A;
+  memset(&A, 0, sizeof A);
+  A.state = (real*)h->f[RCG_FIELD_STATE];
+  A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  A.action = (const real*)h->f[RCG_FIELD_ACTION];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  A.n_sub = n_substeps;
+  return A;
 }
 
 // rcg_loop_step's glue kernel (rcg_loop.hpp): [set ACTION from the pinned host buffer] -> [sim step] -> [stage cost + pack]
@@ -83,13 +132,7 @@ template <typename real>
 static void fill_loop_args(rcg_handle* h, LoopArgs<real>& A, const double* act_in, int32_t n_substeps, int32_t do_sim,
                            int32_t do_tail, int32_t decided, int32_t dc, double* out, double* flag, double seq) {
   memset(&A, 0, sizeof A);
-  A.sim.state = (real*)h->f[RCG_FIELD_STATE];
-  A.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-  A.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
-  A.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
-  A.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-  A.sim.n_sub = n_substeps;
+  A.sim = sim_args<real>(h, n_substeps);
   A.action = (real*)h->f[RCG_FIELD_ACTION];
   A.act_in = act_in;
   A.best_J = (const real*)h->f[RCG_FIELD_BEST_J];
@@ -111,8 +154,7 @@ static int op_loop(rcg_handle* h, const double* act_in, int32_t n_substeps, int3
     LoopArgs<real> A;
     fill_loop_args<real>(h, A, act_in, n_substeps, do_sim, do_tail, decided, dc, out, flag, seq);
     hipLaunchKernelGGL((k_loop<Sys, real>), dim3(blocks_for(h->cfg.batch, 64)), dim3(64), 0, h->stream, A, params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    return launch_done(h);
   });
 }
 
@@ -122,8 +164,7 @@ static int op_critic(rcg_handle* h, const void* obs, const void* act, const void
     using real = decltype(r);
     hipLaunchKernelGGL((k_critic<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, h->stream, (const real*)obs,
                        (const real*)act, (const real*)w, (real*)out, (long)n, params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    return launch_done(h);
   });
 }
 
@@ -135,23 +176,8 @@ static int op_critic_cost(rcg_handle* h, const void* w, void* Jc) {
                        w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC], (const real*)h->f[RCG_FIELD_W_PREV],
                        (const real*)h->f[RCG_FIELD_OBS_BUF], (const real*)h->f[RCG_FIELD_ACT_BUF], (real*)Jc,
                        params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    return launch_done(h);
   });
-}
-
-// the env step's arguments: the handle's own fields (k_sim, k_sim_v, k_sim_dist; rcg_rtc.hip)
-template <typename real>
-static SimArgs<real> sim_args(const rcg_handle* h, int32_t n_substeps) {
-  SimArgs<real> A;
-  A.state = (real*)h->f[RCG_FIELD_STATE];
-  A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-  A.action = (const real*)h->f[RCG_FIELD_ACTION];
-  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.accum = (real*)h->f[RCG_FIELD_ACCUM];
-  A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-  A.n_sub = n_substeps;
-  return A;
 }
 
 template <typename Sys>
@@ -160,6 +186,8 @@ int op_sim_step(rcg_handle* h, int32_t n_substeps) {
     using real = decltype(r);
     const SimArgs<real> A = sim_args<real>(h, n_substeps);
     ProfScope prof_scope(h, RCG_KERNEL_SIM);
+    const bool tgt = (h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0;
+    const dim3 grid(blocks_for(h->cfg.batch)), block(256);
     if (h->cfg.flags & RCG_FLAG_DISTURB) {  // full state [state, disturb] (rcg_disturb.hpp)
       SimDistArgs<real> D;
       D.S = A;
@@ -167,36 +195,20 @@ int op_sim_step(rcg_handle* h, int32_t n_substeps) {
       D.substep_idx = (int32_t*)h->f[RCG_FIELD_SUBSTEP_IDX];
       D.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
       D.D = disturb_pars(h);
-      if (h->cfg.flags & RCG_FLAG_HAS_TARGET)
-        RCG_LAUNCH(h, (k_sim_dist<Sys, real, true>), dim3(blocks_for(h->cfg.batch)), dim3(256), 0, D,
-                           params<real>(h));
-      else
-        RCG_LAUNCH(h, (k_sim_dist<Sys, real, false>), dim3(blocks_for(h->cfg.batch)), dim3(256), 0, D,
-                           params<real>(h));
-      note_launch(h, RCG_KERNEL_SIM, RCG_KID_SIM_DIST, 0, 64);
-      HIPCHK(h, hipGetLastError());
-      return (int)RCG_OK;
+      with_bools([&](auto TGT) { RCG_LAUNCH(h, (k_sim_dist<Sys, real, TGT()>), grid, block, 0, D, params<real>(h)); }, tgt);
+      return launch_done(h, RCG_KERNEL_SIM, RCG_KID_SIM_DIST, 0, 64);
     }
     constexpr long VEC = 16 / (long)sizeof(real);
     // 16 B per lane and component (k_sim_v) pays once the launch is bandwidth- rather than latency-bound, and only for
     // the light dynamics: 2tank at 2^24 envs 4.7 -> 5.6 TB/s; the robots' RK4 (four accurate sin/cos per substep) with
     // VEC envs per lane needs 112 VGPRs instead of 70 and got SLOWER (5.76 -> 5.2 TB/s), so they stay on k_sim
-    note_launch(h, RCG_KERNEL_SIM, RCG_KID_SIM, 0, 64);
     if (Sys::DS <= 2 && h->cfg.batch % VEC == 0 && h->cfg.batch >= (1 << 18)) {
       const dim3 gridv(blocks_for(h->cfg.batch / VEC));
-      if (h->cfg.flags & RCG_FLAG_HAS_TARGET)
-        RCG_LAUNCH(h, (k_sim_v<Sys, real, true>), gridv, dim3(256), 0, A, params<real>(h));
-      else
-        RCG_LAUNCH(h, (k_sim_v<Sys, real, false>), gridv, dim3(256), 0, A, params<real>(h));
-      note_launch(h, RCG_KERNEL_SIM, RCG_KID_SIM_V, 0, 64 * (int)VEC);
-    } else if (h->cfg.flags & RCG_FLAG_HAS_TARGET)
-      RCG_LAUNCH(h, (k_sim<Sys, real, true>), dim3(blocks_for(h->cfg.batch)), dim3(256), 0, A,
-                         params<real>(h));
-    else
-      RCG_LAUNCH(h, (k_sim<Sys, real, false>), dim3(blocks_for(h->cfg.batch)), dim3(256), 0, A,
-                         params<real>(h));
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+      with_bools([&](auto TGT) { RCG_LAUNCH(h, (k_sim_v<Sys, real, TGT()>), gridv, block, 0, A, params<real>(h)); }, tgt);
+      return launch_done(h, RCG_KERNEL_SIM, RCG_KID_SIM_V, 0, 64 * (int)VEC);
+    }
+    with_bools([&](auto TGT) { RCG_LAUNCH(h, (k_sim<Sys, real, TGT()>), grid, block, 0, A, params<real>(h)); }, tgt);
+    return launch_done(h, RCG_KERNEL_SIM, RCG_KID_SIM, 0, 64);
   });
 }
 
@@ -229,29 +241,29 @@ static inline int fit_form_of(int m, int dc, bool force_ml) {
   if (m > 3) return FIT_FORM_ROWS;
   return (dc >= kFitLanesMinDc || force_ml) ? FIT_FORM_3ML : FIT_FORM_3;
 }
-// Fills the kernel arguments and the plan, and sizes the scratch tensor of k_critic_fit_gen; returns RCG_OK or the error of a
-// failed allocation (nothing launched).
+// The critic update's arguments on the handle's own fields (fit_plan, ticks_mem_plan); env_lo / env_hi stay 0: the whole batch
 template <typename real>
-static int fit_plan(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t do_fit, bool force_ml, FitArgs<real>& F, FitPlan& L) {
-  const int m = h->cfg.n_critic - 1;
+static void fit_args(const rcg_handle* h, FitArgs<real>& F, int32_t do_sim, int32_t do_push, int32_t do_fit, int32_t n_substeps) {
   memset(&F, 0, sizeof F);
   F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
   F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
   F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
   F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
   F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
-  F.do_sim = n_substeps > 0;
+  F.do_sim = do_sim;
   F.do_push = do_push;
   F.do_fit = do_fit;
   F.state = (const real*)h->f[RCG_FIELD_STATE];
   F.action = (const real*)h->f[RCG_FIELD_ACTION];
-  F.sim.state = (real*)h->f[RCG_FIELD_STATE];
-  F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-  F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
-  F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
-  F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-  F.sim.n_sub = n_substeps;
+  F.sim = sim_args<real>(h, n_substeps);
+}
+
+// Fills the kernel arguments and the plan, and sizes the scratch tensor of k_critic_fit_gen; returns RCG_OK or the error of a
+// failed allocation (nothing launched).
+template <typename real>
+static int fit_plan(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t do_fit, bool force_ml, FitArgs<real>& F, FitPlan& L) {
+  const int m = h->cfg.n_critic - 1;
+  fit_args<real>(h, F, n_substeps > 0, do_push, do_fit, n_substeps);
   F.env_lo = h->sub_lo;  // (a half of a split tick; 0, 0: the whole batch)
   F.env_hi = h->sub_hi;
   const long n_env = h->sub_hi > 0 ? h->sub_hi - h->sub_lo : h->cfg.batch;
@@ -317,26 +329,16 @@ int op_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_t
 #endif
     const int rc = fit_plan<real>(h, n_substeps, do_push, do_fit, force_ml, F, L);
     if (rc) return rc;
-#define RCG_FIT(CS)                                                                                                    \
-  do {                                                                                                                 \
-    if (L.form == FIT_FORM_3 || L.form == FIT_FORM_3ML)                                                                \
-      launch_fit3<Sys, real, CS>(h, F, L);                                                                             \
-    else if (L.form == FIT_FORM_ROWS)                                                                                  \
-      RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS, kFitMaxRows>), L.grid, L.block, 0, F, h->p64, params<real>(h));       \
-    else                                                                                                               \
-      RCG_LAUNCH(h, (k_critic_fit_gen<Sys, real, CS>), L.grid, L.block, 0, F, h->p64, params<real>(h),                 \
-                 (double*)h->fit_scratch);                                                                             \
-  } while (0)
-    switch (h->cfg.critic_struct) {
-      case RCG_CRITIC_QUAD_LIN: RCG_FIT(RCG_CRITIC_QUAD_LIN); break;
-      case RCG_CRITIC_QUADRATIC: RCG_FIT(RCG_CRITIC_QUADRATIC); break;
-      case RCG_CRITIC_QUAD_NOMIX: RCG_FIT(RCG_CRITIC_QUAD_NOMIX); break;
-      default: RCG_FIT(RCG_CRITIC_QUAD_MIX); break;
-    }
-#undef RCG_FIT
-    note_launch(h, RCG_KERNEL_CRITIC, RCG_KID_CRITIC_FIT, L.variant, L.epw);
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    with_critic(h->cfg.critic_struct, [&](auto CS) {
+      if (L.form == FIT_FORM_3 || L.form == FIT_FORM_3ML)
+        launch_fit3<Sys, real, CS()>(h, F, L);
+      else if (L.form == FIT_FORM_ROWS)
+        RCG_LAUNCH(h, (k_critic_fit<Sys, real, CS(), kFitMaxRows>), L.grid, L.block, 0, F, h->p64, params<real>(h));
+      else
+        RCG_LAUNCH(h, (k_critic_fit_gen<Sys, real, CS()>), L.grid, L.block, 0, F, h->p64, params<real>(h),
+                   (double*)h->fit_scratch);
+    });
+    return launch_done(h, RCG_KERNEL_CRITIC, RCG_KID_CRITIC_FIT, L.variant, L.epw);
   });
 }
 
@@ -403,6 +405,65 @@ static int fit_lanes_knob() { return dev_knobs().fit_lanes; }
 template <typename Sys>
 int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand);
 
+// ---- what the plans below share --------------------------------------------------------------------
+// The decision's inputs (ActorArgs, OptArgs, SearchArgs; `step_idx`: the struct's tick counter, whatever it calls it): the
+// caller's observation or the handle's STATE, the rollout's start, the weights, the tick epilogue's fields.  `w_hint`: the tail
+// of the refusal of missing critic weights, nullptr where the caller has checked them.
+template <template <typename> class Args, typename real>
+static int decision_inputs(rcg_handle* h, const char* who, const void* obs, const void* state_sys, const void* w, bool tick,
+                           const char* w_hint, Args<real>& A, int32_t*& step_idx) {
+  const rcg_cfg& c = h->cfg;
+  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
+  if (state_sys)
+    A.state_sys = (const real*)state_sys;
+  else if (obs)
+    A.state_sys = (const real*)obs;
+  else
+    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
+  // without an observation the kernel is handed the handle's STATE and observes y_0 = out(STATE) (identity for the built-ins);
+  // an observation [dy][B] is not a state when dy != ds, so it needs state_sys
+  A.obs_x = obs ? 0 : 1;
+  if (obs && !state_sys && h->dy != h->ds)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: an observation of dim_output %d != dim_state %d needs state_sys", who, h->dy, h->ds);
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.w = w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC];
+  if (w_hint && c.mode != RCG_MODE_MPC && !A.w)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: RQL/SQL need critic weights (buffer_size > 0%s)", who, w_hint);
+  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
+  step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
+  return RCG_OK;
+}
+
+// K candidates per env as tiles of 64 lanes: whole tiles from K = 64 on, else 64 / Kp envs per tile (ActorArgs, TicksArgs)
+template <typename Args>
+static void tile_candidates(Args& A, int K) {
+  A.K = K;
+  if (K >= 64) {
+    A.Kp = 64;
+    A.G = 1;
+    A.n_tiles = (K + 63) / 64;
+  } else {
+    int kp = 1;
+    while (kp < K) kp <<= 1;
+    A.Kp = kp;
+    A.G = 64 / kp;
+    A.n_tiles = 1;
+  }
+  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+}
+// levels per input of the generated grid of K candidates (du = 2: a square K, which actor_plan checks)
+static inline int grid_side(int DU, int K) { return DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9); }
+
+// Generated level grid in the regime every preset benchmark runs (float, MPC, the preset's diagonal R1 with its zero
+// weights `zw_preset`, gamma == 1, no target, K = g * g a multiple of 256 with 64 % g == 0): the instances that hold the
+// hand-packed four-tile rollout and nothing else (rcg_kernels.hpp::GenPk: k_actor's, k_ticks_pk)
+template <typename real, typename Args>
+static bool gen_pk_ok(const rcg_handle* h, const KParams<real>& P, unsigned zw_preset, const void* cand, int K, bool generic,
+                      bool tgt, const Args& A) {
+  return !cand && !generic && !tgt && h->cfg.gamma == 1.0 && zw_preset != 0u && (P.zero_w & zw_preset) == zw_preset && K >= 256 &&
+         A.n_tiles % 4 == 0 && A.grid_g > 0 && (64 % A.grid_g) == 0 && !A.no_multi && !dev_knobs().no_pk;
+}
+
 // ---- k_actor / k_actor_dma ---------------------------------------------------------------------
 // The decision step's launch geometry: what launch_actor decides from runtime values alone - row length, K, the system's
 // dimensions and observation-target preset, element size, batch, mode and stage cost - before it picks a kernel instance.
@@ -416,6 +477,7 @@ struct ActorPlan {
   int wpb;                     // k_actor: waves per block, dynamic LDS, blocks
   size_t lds;
   unsigned blocks;
+  int word;                    // k_actor's rcg_last_launch word (bit 4: the DIRECT form)
   int variant;                 // k_actor_dma / k_actor_dma_packed variant (DMA_*)
   bool dma_ok, pack_ok;        // the shape goes to k_actor_dma / k_actor_dma_packed
   bool fuse_sim;               // k_actor_dma_packed steps its own envs in its prologue (sim_first)
@@ -438,51 +500,20 @@ static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_t
   if (K < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: K must be >= 1", who);
   memset(&A, 0, sizeof A);
   A.cand = (const real*)cand;
-  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
-  if (state_sys)
-    A.state_sys = (const real*)state_sys;
-  else if (obs)
-    A.state_sys = (const real*)obs;
-  else
-    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-  // without an observation the kernel is handed the handle's STATE and observes y_0 = out(STATE) (identity for the built-ins);
-  // an observation [dy][B] is not a state when dy != ds, so it needs state_sys
-  A.obs_x = obs ? 0 : 1;
-  if (obs && !state_sys && h->dy != h->ds)
-    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: an observation of dim_output %d != dim_state %d needs state_sys", who, h->dy, h->ds);
-  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.w = w ? (const real*)w : (const real*)h->f[RCG_FIELD_W_CRITIC];
-  if (c.mode != RCG_MODE_MPC && !A.w)
-    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: RQL/SQL need critic weights (buffer_size > 0 or an explicit w)", who);
+  {
+    const int rc = decision_inputs(h, who, obs, state_sys, w, tick, " or an explicit w", A, A.step_idx);
+    if (rc) return rc;
+  }
   A.J = (real*)J;
   A.action_out = (real*)action;
   A.best_J = (real*)best_J;
   A.best_idx = best_idx;
-  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-  A.step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
-  A.K = K;
-  if (K >= 64) {
-    A.Kp = 64;
-    A.G = 1;
-    A.n_tiles = (K + 63) / 64;
-  } else {
-    int kp = 1;
-    while (kp < K) kp <<= 1;
-    A.Kp = kp;
-    A.G = 64 / kp;
-    A.n_tiles = 1;
-  }
-  A.grid_g = 0;
-  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+  tile_candidates(A, K);
   if (!cand) {
-    if (DU == 1) {
-      A.grid_g = K;
-    } else {
-      int g = (int)std::floor(std::sqrt((double)K) + 1e-9);
-      if (g * g != K)
-        return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: generated grid for du = 2 needs a square K (got %d)", who, K);
-      A.grid_g = g;
-    }
+    const int g = grid_side(DU, K);
+    if (DU != 1 && g * g != K)
+      return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: generated grid for du = 2 needs a square K (got %d)", who, K);
+    A.grid_g = g;
   }
   const int R = c.n_actor * DU;
   const size_t row_bytes = (size_t)R * sizeof(real);
@@ -508,6 +539,7 @@ static int actor_plan(rcg_handle* h, const char* who, int DS, int DU, bool sys_t
   const bool tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
   L.generic = generic;
   L.tgt = tgt;
+  L.word = long_row ? (1 | (tgt ? 2 : 0) | 4 | 16) : ((generic ? 1 : 0) | (tgt ? 2 : 0) | (cand ? 4 : 0));
 
   // Production shape -> k_actor_dma (rcg_actor_dma.hpp): streamed candidates, K >= 33 with K * R * esz % 16 == 0 (33 .. 63: one
   // ragged tile per env - K = 48: 4.6 TB/s against 2.9 on k_actor, K = 36: 3.6 against 2.3 (RQL: 3.1 x, profiles/r04_ab_min_k.txt); at K <= 32 k_actor, which packs 64 / K envs into a tile,
@@ -635,11 +667,12 @@ static ActorArgs<real> packed_args(const rcg_handle* h, const ActorArgs<real>& A
   Ap.gpw = (int)L.pack_gpw;
   Ap.jwave = 1;
   if (L.fuse_sim) {
-    Ap.sim_state = (real*)h->f[RCG_FIELD_STATE];
-    Ap.sim_state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-    Ap.sim_action = (const real*)h->f[RCG_FIELD_ACTION];
-    Ap.sim_status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-    Ap.sim_n_sub = h->cfg.substeps_per_tick;
+    const SimArgs<real> S = sim_args<real>(h, h->cfg.substeps_per_tick);
+    Ap.sim_state = S.state;
+    Ap.sim_state_prev = S.state_prev;
+    Ap.sim_action = S.action;
+    Ap.sim_status = S.status;
+    Ap.sim_n_sub = S.n_sub;
   }
   return Ap;
 }
@@ -653,6 +686,22 @@ static ActorArgs<real> dma_args(const rcg_handle* h, const ActorArgs<real>& A, c
   return Ad;
 }
 
+// What a decision launcher answers from the plan alone (true: return rc, nothing launched): rcg_control_tick's probe - asked,
+// before it launches anything, whether this tick's decision runs on k_actor_dma - and the refusal of a split tick that does not
+static inline bool actor_plan_answers(rcg_handle* h, const char* who, const ActorPlan& L, int& rc) {
+  const bool dma = L.dma_ok && !L.pack_ok;
+  if (h->probe == 1) {
+    h->probe = dma ? 3 : 2;
+    rc = RCG_OK;
+    return true;
+  }
+  if (h->sub_hi > 0 && !dma) {
+    rc = rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: a split tick needs the k_actor_dma shape", who);
+    return true;
+  }
+  return false;
+}
+
 template <typename Sys, typename real>
 static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K, const void* obs,
                         const void* state_sys, const void* w, void* J, void* action, void* best_J, int32_t* best_idx,
@@ -660,131 +709,78 @@ static int launch_actor(rcg_handle* h, const char* who, const void* cand, int K,
   const rcg_cfg& c = h->cfg;
   ActorArgs<real> A;
   ActorPlan L;
-  {
-    const int rc = actor_plan<real>(h, who, Sys::DS, Sys::DU, Sys::TGT, cand, K, obs, state_sys, w, J, action, best_J, best_idx,
-                                    tick, sim_first, A, L);
-    if (rc) return rc;
-  }
+  int rc = actor_plan<real>(h, who, Sys::DS, Sys::DU, Sys::TGT, cand, K, obs, state_sys, w, J, action, best_J, best_idx, tick,
+                            sim_first, A, L);
+  if (rc || actor_plan_answers(h, who, L, rc)) return rc;
   const KParams<real>& P = params<real>(h);
-  const DevKnobs& knobs = dev_knobs();
-  const int R = L.R, wpb = L.wpb, variant = L.variant;
-  const size_t lds = L.lds;
-  const unsigned blocks = L.blocks;
-  const bool generic = L.generic, tgt = L.tgt, dma_ok = L.dma_ok, pack_ok = L.pack_ok, fuse_sim = L.fuse_sim;
+  const dim3 grid(L.blocks), block(64 * L.wpb);
   // rcg_control_tick with the generated grid in the regime of the hand-packed rollout: env step and decision in ONE launch
   // (k_ticks_pk with T = 1 - what rcg_control_ticks runs, so the two entry points cannot differ by a bit)
-  if (h->probe == 1) {  // rcg_control_tick asking, before it launches anything, whether this tick's decision runs on k_actor_dma
-    h->probe = (dma_ok && !pack_ok) ? 3 : 2;
-    return RCG_OK;
-  }
-  if (h->sub_hi > 0 && !(dma_ok && !pack_ok))
-    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: a split tick needs the k_actor_dma shape", who);
   if constexpr (std::is_same<real, float>::value && GenPk<Sys>::supported && GenPk<Sys>::fuse_tick) {
-    if (tick && sim_first && !cand && !generic && !tgt && c.gamma == 1.0 && Sys::ZW_PRESET != 0u &&
-        (P.zero_w & Sys::ZW_PRESET) == Sys::ZW_PRESET && K >= 256 && A.n_tiles % 4 == 0 && A.grid_g > 0 &&
-        (64 % A.grid_g) == 0 && !A.no_multi && !knobs.no_pk && !knobs.no_tick_fuse && !(c.flags & RCG_FLAG_DISTURB) && !obs &&
-        !state_sys &&
-        action == h->f[RCG_FIELD_ACTION] && best_J == h->f[RCG_FIELD_BEST_J] && (void*)best_idx == h->f[RCG_FIELD_BEST_IDX])
+    if (tick && sim_first && gen_pk_ok(h, P, Sys::ZW_PRESET, cand, K, L.generic, L.tgt, A) && !dev_knobs().no_tick_fuse &&
+        !(c.flags & RCG_FLAG_DISTURB) && !obs && !state_sys && action == h->f[RCG_FIELD_ACTION] &&
+        best_J == h->f[RCG_FIELD_BEST_J] && (void*)best_idx == h->f[RCG_FIELD_BEST_IDX])
       return op_ticks<Sys>(h, 1, K, nullptr);
   }
-  if (sim_first && !fuse_sim) {
-    int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
+  if (sim_first && !L.fuse_sim) {
+    rc = op_sim_step<Sys>(h, c.substeps_per_tick);
     if (rc) return rc;
   }
   ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
-  if (pack_ok) {
+  if (L.pack_ok) {
     const ProfPair pp = prof_take(h);  // a due ProfScope's pair travels in the dispatch
     const ActorArgs<real> Ap = packed_args(h, A, L);
-    const dim3 grid = L.pack_grid, block(256);
-    const size_t lds_req = L.pack_lds;
     // (no instance - RQL / SQL with more than 36 dwords of weights: the tick is served by k_actor_dma / k_actor below)
+    const int v = L.variant;
+    const dim3 blk(256);
     const bool launched =
-        variant < DMA_RQL_0    ? launch_dma_packed<Sys, real, 3>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b)
-        : variant >= DMA_SQL_0 ? launch_dma_packed<Sys, real, 4>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b)
-                               : launch_dma_packed<Sys, real, 5>(R, variant, grid, block, lds_req, h->stream, Ap, P, pp.a, pp.b);
-    if (launched) {
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA_PACKED, variant | (fuse_sim ? 16 : 0), (int)L.pack_gpw);
-      HIPCHK(h, hipGetLastError());
-      return RCG_OK;
-    }
+        v < DMA_RQL_0    ? launch_dma_packed<Sys, real, 3>(L.R, v, L.pack_grid, blk, L.pack_lds, h->stream, Ap, P, pp.a, pp.b)
+        : v >= DMA_SQL_0 ? launch_dma_packed<Sys, real, 4>(L.R, v, L.pack_grid, blk, L.pack_lds, h->stream, Ap, P, pp.a, pp.b)
+                         : launch_dma_packed<Sys, real, 5>(L.R, v, L.pack_grid, blk, L.pack_lds, h->stream, Ap, P, pp.a, pp.b);
+    if (launched)
+      return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA_PACKED, v | (L.fuse_sim ? 16 : 0), (int)L.pack_gpw);
     prof_give_back(h, pp);
-    if (fuse_sim) {  // no packed instance after all: the env step as its own launch, then the other kernels
-      int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
+    if (L.fuse_sim) {  // no packed instance after all: the env step as its own launch, then the other kernels
+      rc = op_sim_step<Sys>(h, c.substeps_per_tick);
       if (rc) return rc;
     }
   }
-  if (dma_ok) {
+  if (L.dma_ok) {
     const ActorArgs<real> Ad = dma_args(h, A, L);
-    const dim3 grid = L.dma_grid, block(256);
-    const size_t lds_req = L.dma_lds;
-    bool ok = false;
     const ProfPair pp = prof_take(h);  // a due ProfScope's pair travels in the dispatch
-    if (variant >= DMA_RQL_GEN_0)
-      ok = launch_dma<Sys, real, 7>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
-    else if (variant >= DMA_MPC_GEND)
-      ok = launch_dma<Sys, real, 6>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
-    else if (variant < DMA_RQL_0)
-      ok = launch_dma<Sys, real, 0>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
-    else if (variant >= DMA_SQL_0)
-      ok = launch_dma<Sys, real, 1>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
+    const int v = L.variant;
+    const dim3 blk(256);
+    bool ok;
+    if (v >= DMA_RQL_GEN_0)
+      ok = launch_dma<Sys, real, 7>(L.R, v, L.dma_grid, blk, L.dma_lds, h->stream, Ad, P, pp.a, pp.b);
+    else if (v >= DMA_MPC_GEND)
+      ok = launch_dma<Sys, real, 6>(L.R, v, L.dma_grid, blk, L.dma_lds, h->stream, Ad, P, pp.a, pp.b);
+    else if (v < DMA_RQL_0)
+      ok = launch_dma<Sys, real, 0>(L.R, v, L.dma_grid, blk, L.dma_lds, h->stream, Ad, P, pp.a, pp.b);
+    else if (v >= DMA_SQL_0)
+      ok = launch_dma<Sys, real, 1>(L.R, v, L.dma_grid, blk, L.dma_lds, h->stream, Ad, P, pp.a, pp.b);
     else
-      ok = launch_dma<Sys, real, 2>(R, variant, grid, block, lds_req, h->stream, Ad, P, pp.a, pp.b);
-    if (!ok) prof_give_back(h, pp);
+      ok = launch_dma<Sys, real, 2>(L.R, v, L.dma_grid, blk, L.dma_lds, h->stream, Ad, P, pp.a, pp.b);
     if (ok) {  // (otherwise - unreachable for the rows dma_ok admits - k_actor below serves the tick: never refused half-way)
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, variant, (int)L.dma_gpw);
-      h->last[RCG_KERNEL_ACTOR].zero_w = dma_zero_w<real>(dma_zw_preset<Sys, real>(), variant, Ad, P);  // launch_dma's rule
-      HIPCHK(h, hipGetLastError());
-      return RCG_OK;
+      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_DMA, v, (int)L.dma_gpw);
+      h->last[RCG_KERNEL_ACTOR].zero_w = dma_zero_w<real>(dma_zw_preset<Sys, real>(), v, Ad, P);  // launch_dma's rule
+      return launch_done(h);
     }
+    prof_give_back(h, pp);
   }
-  // Generated level grid in the regime every preset benchmark runs (float, MPC, the preset's diagonal R1 with its zero
-  // weights, gamma == 1, no target, K = g * g a multiple of 256 with 64 % g == 0): the instance that holds the hand-packed
-  // four-tile rollout and nothing else (rcg_kernels.hpp::GenPk)
+  // the generated grid's hand-packed instance (gen_pk_ok)
   if constexpr (std::is_same<real, float>::value && GenPk<Sys>::supported) {
-    const bool pk_ok = !cand && !generic && !tgt && c.gamma == 1.0 && Sys::ZW_PRESET != 0u &&
-                       (P.zero_w & Sys::ZW_PRESET) == Sys::ZW_PRESET && K >= 256 && A.n_tiles % 4 == 0 && A.grid_g > 0 &&
-                       (64 % A.grid_g) == 0 && !A.no_multi && !knobs.no_pk;
-    if (pk_ok) {
-      RCG_LAUNCH(h, (k_actor<Sys, real, false, false, false, true>), dim3(blocks), dim3(64 * wpb), lds, A, P);
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, 8, A.G);  // variant bit 3: the packed instance
-      HIPCHK(h, hipGetLastError());
-      return RCG_OK;
+    if (gen_pk_ok(h, P, Sys::ZW_PRESET, cand, K, L.generic, L.tgt, A)) {
+      RCG_LAUNCH(h, (k_actor<Sys, real, false, false, false, true>), grid, block, L.lds, A, P);
+      return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, 8, A.G);  // variant bit 3: the packed instance
     }
   }
-  if (L.long_row) {
-    if (tgt)
-      RCG_LAUNCH(h, (k_actor<Sys, real, true, true, true, false, true>), dim3(blocks), dim3(64 * wpb), 0, A, P);
-    else
-      RCG_LAUNCH(h, (k_actor<Sys, real, true, false, true, false, true>), dim3(blocks), dim3(64 * wpb), 0, A, P);
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, 1 | (tgt ? 2 : 0) | 4 | 16, A.G);  // variant bit 4: DIRECT rows
-    HIPCHK(h, hipGetLastError());
-    return RCG_OK;
-  }
-#define RCG_LAUNCH_ACTOR(GEN, TGT, STR) \
-  RCG_LAUNCH(h, (k_actor<Sys, real, GEN, TGT, STR>), dim3(blocks), dim3(64 * wpb), lds, A, P)
-#define RCG_LAUNCH_ACTOR2(GEN, TGT)      \
-  do {                                   \
-    if (cand)                            \
-      RCG_LAUNCH_ACTOR(GEN, TGT, true);  \
-    else                                 \
-      RCG_LAUNCH_ACTOR(GEN, TGT, false); \
-  } while (0)
-  if (generic) {
-    if (tgt)
-      RCG_LAUNCH_ACTOR2(true, true);
-    else
-      RCG_LAUNCH_ACTOR2(true, false);
-  } else {
-    if (tgt)
-      RCG_LAUNCH_ACTOR2(false, true);
-    else
-      RCG_LAUNCH_ACTOR2(false, false);
-  }
-#undef RCG_LAUNCH_ACTOR2
-#undef RCG_LAUNCH_ACTOR
-  note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, (generic ? 1 : 0) | (tgt ? 2 : 0) | (cand ? 4 : 0), A.G);
-  HIPCHK(h, hipGetLastError());
-  return RCG_OK;
+  if (L.long_row)  // the DIRECT form exists for the generic streamed instance alone
+    with_bools([&](auto TGT) { RCG_LAUNCH(h, (k_actor<Sys, real, true, TGT(), true, false, true>), grid, block, 0, A, P); }, L.tgt);
+  else
+    with_bools([&](auto GEN, auto TGT, auto STR) { RCG_LAUNCH(h, (k_actor<Sys, real, GEN(), TGT(), STR()>), grid, block, L.lds, A, P); },
+               L.generic, L.tgt, cand != nullptr);
+  return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR, L.word, A.G);
 }
 
 template <typename Sys>
@@ -796,35 +792,32 @@ int op_actor(rcg_handle* h, const char* who, const void* cand, int K, const void
   });
 }
 
-// k_actor_opt's arguments and launch shape for the handle (the built-in systems' launcher below and rcg_rtc.hip): fills A, the
-// waves per block and the block's LDS; refuses (nothing launched) a working set beyond the CU's 160 KB
+// k_actor_opt's arguments and launch shape for the handle (the built-in systems' launcher below and rcg_rtc.hip, which
+// therefore pick the same instance, geometry and variant word for a registered copy of a built-in system)
+struct OptPlan {
+  bool generic, tgt, pairs;  // the instance: k_actor_opt<Sys, real, tgt, generic, pairs>; pairs: the curvature pairs and the
+                             // four-lanes-per-env phase 1b
+  int wpb;                   // waves per workgroup (a wave owns OPT_G envs)
+  size_t lds;
+  dim3 grid, block;
+  int variant;               // rcg_last_launch (the LOOP instances add bit 3)
+};
+
+// Fills A and L; refuses (nothing launched) a bad argument or a working set beyond the CU's 160 KB
 template <typename real>
 static int opt_plan(rcg_handle* h, int du, int32_t iters, const void* obs, const void* state_sys, const void* u_init, int shift,
-                    void* u_opt, void* action, void* best_J, int32_t* n_iter, bool tick, OptArgs<real>& A, int& wpb, size_t& lds) {
+                    void* u_opt, void* action, void* best_J, int32_t* n_iter, bool tick, OptArgs<real>& A, OptPlan& L) {
   const rcg_cfg& c = h->cfg;
   memset(&A, 0, sizeof A);
-  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
-  if (state_sys)
-    A.state_sys = (const real*)state_sys;
-  else if (obs)
-    A.state_sys = (const real*)obs;
-  else
-    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-  A.obs_x = obs ? 0 : 1;  // as actor_plan
-  if (obs && !state_sys && h->dy != h->ds)
-    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_optimize: an observation of dim_output %d != dim_state %d needs state_sys", h->dy,
-                    h->ds);
-  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
-  if (c.mode != RCG_MODE_MPC && !A.w)
-    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_optimize: RQL/SQL need critic weights (buffer_size > 0)");
+  {
+    const int rc = decision_inputs(h, "rcg_actor_optimize", obs, state_sys, nullptr, tick, "", A, A.step_idx);
+    if (rc) return rc;
+  }
   A.u_init = (const real*)u_init;
   A.u_opt = (real*)u_opt;
   A.action_out = (real*)action;
   A.best_J = (real*)best_J;
   A.n_iter = n_iter;
-  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-  A.step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
   for (int i = 0; i < du; ++i) A.u0[i] = (real)c.action_init[i];
   A.iters = iters;
   A.shift = shift;
@@ -835,7 +828,7 @@ static int opt_plan(rcg_handle* h, int du, int32_t iters, const void* obs, const
   // 160 KB: 4 (one per SIMD) unless 2 or 1 bring more waves onto the CU (quad-mix on the 3-wheel robot with 4 pairs: 20.4 KB
   // per wave = ONE block of four, but seven blocks of one; long horizons in f64: N = 20, 4 pairs needs 70 KB per wave)
   const size_t lds_wave = opt_wave_lds_bytes(h);
-  wpb = 4;
+  int wpb = 4;
   size_t on_cu = 0;
   for (int cand_wpb = 4; cand_wpb >= 1; cand_wpb >>= 1) {
     const size_t fit = lds_wave * cand_wpb ? ((size_t)160 * 1024 / (lds_wave * cand_wpb)) * cand_wpb : 0;
@@ -845,11 +838,20 @@ static int opt_plan(rcg_handle* h, int du, int32_t iters, const void* obs, const
       wpb = cand_wpb;
     }
   }
-  lds = lds_wave * wpb;
+  const size_t lds = lds_wave * wpb;
   if (lds > (size_t)160 * 1024)
     return rcg_fail(h, RCG_ERR_UNSUPPORTED,
                     "rcg_actor_optimize: horizon %d with %d curvature pairs needs %zu B of LDS per wave (rcg_set_optimizer)",
                     c.n_actor, opt_memory_of(h), lds_wave);
+  // (RQL / SQL run on the generic instance; its critic terms are over [y, u])
+  L.generic = !(c.mode == RCG_MODE_MPC && params<real>(h).stage_kind == 0);
+  L.tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  L.pairs = A.memory > 0;
+  L.wpb = wpb;
+  L.lds = lds;
+  L.grid = dim3(blocks_for(c.batch, wpb * OPT_G));
+  L.block = dim3(64 * wpb);
+  L.variant = (L.generic ? 1 : 0) | (L.tgt ? 2 : 0) | (L.pairs ? 4 : 0);
   return RCG_OK;
 }
 
@@ -861,56 +863,35 @@ int op_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* state
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     OptArgs<real> A;
-    int wpb;
-    size_t lds;
-    {
-      const int rc = opt_plan<real>(h, Sys::DU, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, wpb, lds);
-      if (rc) return rc;
-    }
+    OptPlan L;
+    int rc = opt_plan<real>(h, Sys::DU, iters, obs, state_sys, u_init, shift, u_opt, action, best_J, n_iter, tick, A, L);
+    if (rc) return rc;
     const bool loop = h->loop_io.on;  // rcg_loop_step's one-launch sample: head and tail of the loop iteration in this launch
     if (loop)
       fill_loop_args<real>(h, A.loop, h->loop_io.act_in, h->loop_io.n_substeps, 1, 1, 1, h->loop_io.dc, h->loop_io.out,
                            h->loop_io.flag, h->loop_io.seq);
-    const bool generic = !(c.mode == RCG_MODE_MPC && P.stage_kind == 0);
-    const dim3 grid(blocks_for(c.batch, wpb * OPT_G)), block(64 * wpb);  // a wave owns OPT_G envs
-    const bool tgt = c.flags & RCG_FLAG_HAS_TARGET;
     if (tick && sim_first) {  // rcg_control_tick_opt (MPC): the env step of the tick, once every argument check has passed
-      const int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
+      rc = op_sim_step<Sys>(h, c.substeps_per_tick);
       if (rc) return rc;
     }
-    const bool pairs = A.memory > 0;  // the instance with the curvature pairs and the four-lanes-per-env phase 1b
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
-#define RCG_OPT_LAUNCH(T, GEN, PR)                                                                                  \
-  do {                                                                                                              \
-    auto fn = k_actor_opt<Sys, real, T, GEN, PR>;                                                                   \
-    if (lds > 64 * 1024) /* beyond the default dynamic-LDS limit (the CU has 160 KB) */                             \
-      HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, \
-                                    (int)lds));                                                                     \
-    RCG_LAUNCH(h, fn, grid, block, lds, A, P);                                                                      \
-  } while (0)
-    const int sel = (generic ? 4 : 0) | (tgt ? 2 : 0) | (pairs ? 1 : 0);
-    if (loop) {  // (rcg_loop_step asks only where opt_plain_instance() holds)
-      if (generic || pairs || obs || state_sys != h->f[RCG_FIELD_STATE_PREV] || u_init || tick)
+    auto go = [&](auto fn) {
+      if (L.lds > 64 * 1024)  // beyond the default dynamic-LDS limit (the CU has 160 KB)
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+      RCG_LAUNCH(h, fn, L.grid, L.block, L.lds, A, P);
+      return (int)RCG_OK;
+    };
+    if (loop) {  // (rcg_loop_step asks only where opt_plain_instance() holds); the LOOP instances: plain MPC alone
+      if (L.generic || L.pairs || obs || state_sys != h->f[RCG_FIELD_STATE_PREV] || u_init || tick)
         return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: the one-launch sample is the plain MPC instance on the handle's own fields");
-      auto fn = tgt ? k_actor_opt<Sys, real, true, false, false, true> : k_actor_opt<Sys, real, false, false, false, true>;
-      if (lds > 64 * 1024)
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      RCG_LAUNCH(h, fn, grid, block, lds, A, P);
-    } else
-    switch (sel) {
-      case 0: RCG_OPT_LAUNCH(false, false, false); break;
-      case 1: RCG_OPT_LAUNCH(false, false, true); break;
-      case 2: RCG_OPT_LAUNCH(true, false, false); break;
-      case 3: RCG_OPT_LAUNCH(true, false, true); break;
-      case 4: RCG_OPT_LAUNCH(false, true, false); break;
-      case 5: RCG_OPT_LAUNCH(false, true, true); break;
-      case 6: RCG_OPT_LAUNCH(true, true, false); break;
-      default: RCG_OPT_LAUNCH(true, true, true); break;
+      rc = with_bools([&](auto TGT) { return go(k_actor_opt<Sys, real, TGT(), false, false, true>); }, L.tgt);
+    } else {
+      // (asked in the negative, which keeps the instances' order in the code object: plain MPC first, the pairs innermost)
+      rc = with_bools([&](auto NG, auto NT, auto NP) { return go(k_actor_opt<Sys, real, !NT(), !NG(), !NP()>); }, !L.generic,
+                      !L.tgt, !L.pairs);
     }
-#undef RCG_OPT_LAUNCH
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, (generic ? 1 : 0) | (tgt ? 2 : 0) | (pairs ? 4 : 0) | (loop ? 8 : 0), OPT_G);
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    if (rc) return rc;
+    return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, L.variant | (loop ? 8 : 0), OPT_G);
   });
 }
 
@@ -941,26 +922,15 @@ static int search_plan(rcg_handle* h, int du, bool sys_tgt, int32_t K, int32_t r
   const rcg_cfg& c = h->cfg;
   const KParams<real>& P = params<real>(h);
   memset(&A, 0, sizeof A);
-  A.obs = obs ? (const real*)obs : (const real*)h->f[RCG_FIELD_STATE];
-  if (state_sys)
-    A.state_sys = (const real*)state_sys;
-  else if (obs)
-    A.state_sys = (const real*)obs;
-  else
-    A.state_sys = (const real*)h->f[(tick && (c.flags & RCG_FLAG_REF_LAG)) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-  A.obs_x = obs ? 0 : 1;  // as actor_plan
-  if (obs && !state_sys && h->dy != h->ds)
-    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_actor_search: an observation of dim_output %d != dim_state %d needs state_sys", h->dy,
-                    h->ds);
-  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
+  {  // (the caller has checked the critic weights)
+    const int rc = decision_inputs(h, "rcg_actor_search", obs, state_sys, nullptr, tick, nullptr, A, A.step_rw);
+    if (rc) return rc;
+  }
   A.centre_in = (const real*)centre;
   A.u_best = (real*)u_best;
   A.action_out = (real*)action;
   A.best_J = (real*)best_J;
   A.best_idx = best_idx;
-  A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-  A.step_rw = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
   A.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
   A.step_idx = (const int32_t*)h->f[RCG_FIELD_STEP_IDX];
   for (int i = 0; i < du; ++i) A.u0[i] = (real)c.action_init[i];
@@ -1006,37 +976,25 @@ int op_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const vo
     const KParams<real>& P = params<real>(h);
     SearchArgs<real> A;
     SearchPlan L;
-    {
-      const int rc = search_plan<real>(h, Sys::DU, Sys::TGT, K, rounds, round0, obs, state_sys, centre, shift, u_best, action,
-                                       best_J, best_idx, tick, A, L);
-      if (rc) return rc;
-    }
-    const bool generic = L.generic, tgt = L.tgt;
-    const int nc = L.nc;
-    const dim3 grid = L.grid, block = L.block;
-    const size_t lds = L.lds;
+    int rc = search_plan<real>(h, Sys::DU, Sys::TGT, K, rounds, round0, obs, state_sys, centre, shift, u_best, action, best_J,
+                               best_idx, tick, A, L);
+    if (rc) return rc;
     if (tick && sim_first) {
-      const int rc = op_sim_step<Sys>(h, c.substeps_per_tick);
+      rc = op_sim_step<Sys>(h, c.substeps_per_tick);
       if (rc) return rc;
     }
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
-    if (nc == 3)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 3>), grid, block, lds, A, P);
-    else if (nc == 5)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 5>), grid, block, lds, A, P);
-    else if (nc == 10)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 10>), grid, block, lds, A, P);
-    else if (generic && tgt)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, true, true, 0>), grid, block, lds, A, P);
-    else if (generic)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, true, false, 0>), grid, block, lds, A, P);
-    else if (tgt)
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, true, 0>), grid, block, lds, A, P);
+    // (the register-row instances exist for the system's own TGT alone - search_plan gives nc > 0 only there)
+    if (L.nc == 3)
+      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 3>), L.grid, L.block, L.lds, A, P);
+    else if (L.nc == 5)
+      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 5>), L.grid, L.block, L.lds, A, P);
+    else if (L.nc == 10)
+      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, Sys::TGT, 10>), L.grid, L.block, L.lds, A, P);
     else
-      RCG_LAUNCH(h, (k_actor_search<Sys, real, false, false, 0>), grid, block, lds, A, P);
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_SEARCH, L.variant, 1);
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+      with_bools([&](auto GEN, auto TGT) { RCG_LAUNCH(h, (k_actor_search<Sys, real, GEN(), TGT(), 0>), L.grid, L.block, L.lds, A, P); },
+                 L.generic, L.tgt);
+    return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_SEARCH, L.variant, 1);
   });
 }
 
@@ -1074,20 +1032,8 @@ static int ticks_plan(rcg_handle* h, int DU, int32_t T, int32_t K, const void* c
   }
   A.T = T;
   A.n_sub = c.substeps_per_tick;
-  A.K = K;
-  if (K >= 64) {  // the tiling of launch_actor
-    A.Kp = 64;
-    A.G = 1;
-    A.n_tiles = (K + 63) / 64;
-  } else {
-    int kp = 1;
-    while (kp < K) kp <<= 1;
-    A.Kp = kp;
-    A.G = 64 / kp;
-    A.n_tiles = 1;
-  }
-  A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
-  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+  tile_candidates(A, K);
+  A.grid_g = cand ? 0 : grid_side(DU, K);
   const long n_waves = (c.batch + A.G - 1) / A.G;
   L.generic = P.stage_kind != 0;
   L.tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
@@ -1124,19 +1070,12 @@ int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     const KParams<real>& P = params<real>(h);
     TicksArgs<real> A;
     TicksPlan L;
-    {
-      const int rc = ticks_plan<real>(h, Sys::DU, T, K, cand, A, L);
-      if (rc) return rc;
-    }
-    const bool generic = L.generic, tgt = L.tgt;
-    const size_t lds = L.lds;
-    const dim3 grid = L.grid, block = L.block;
+    const int rc = ticks_plan<real>(h, Sys::DU, T, K, cand, A, L);
+    if (rc) return rc;
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
     if constexpr (std::is_same<real, float>::value && GenPk<Sys>::supported) {
-      const bool pk_ok = !cand && !A.dist && !generic && !tgt && c.gamma == 1.0 && Sys::ZW_PRESET != 0u &&
-                         (P.zero_w & Sys::ZW_PRESET) == Sys::ZW_PRESET && K >= 256 && A.n_tiles % 4 == 0 &&
-                         (64 % A.grid_g) == 0 && !A.no_multi && !dev_knobs().no_pk;
-      if (pk_ok) {  // the kernel around the hand-packed rollout (k_ticks_pk): several envs per wave
+      // the kernel around the hand-packed rollout (k_ticks_pk): several envs per wave
+      if (gen_pk_ok(h, P, Sys::ZW_PRESET, cand, K, L.generic, L.tgt, A) && !A.dist) {
         // envs per wave: a power of two <= 8 that leaves >= 2048 waves (two per SIMD), so that a wave's loads, the env step
         // (one RK4 for all of its envs) and its stores are amortised without unbalancing the launch (65 536 envs, one tick, us
         // per launch by envs per wave: 1: 93.5, 2: 75.6, 4: 67.0, 8: 63.8, 16: 65.1 - profiles/r04_ab_ticks_pk.txt).  Alone, a
@@ -1149,36 +1088,20 @@ int op_ticks(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
         if (dev_knobs().gpw > 0 && dev_knobs().gpw <= 64) gpw = (int)dev_knobs().gpw;
         A.gpw = gpw;
         const long pw = ((long)c.batch + gpw - 1) / gpw;
-        RCG_LAUNCH(h, (k_ticks_pk<Sys>), dim3((unsigned)((pw + 3) / 4)), block, 0, A, P);
-        note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, 8, gpw);
-        HIPCHK(h, hipGetLastError());
-        return (int)RCG_OK;
+        RCG_LAUNCH(h, (k_ticks_pk<Sys>), dim3((unsigned)((pw + 3) / 4)), L.block, 0, A, P);
+        return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, 8, gpw);
       }
     }
-#define RCG_TICKS(GEN, TGT)                                                             \
-  do {                                                                                  \
-    if (cand)                                                                           \
-      RCG_LAUNCH(h, (k_ticks<Sys, real, GEN, TGT, true>), grid, block, lds, A, P);     \
-    else                                                                                \
-      RCG_LAUNCH(h, (k_ticks<Sys, real, GEN, TGT, false>), grid, block, 0, A, P);      \
-  } while (0)
-    if (lds > 64 * 1024) {
-      const void* fn = generic ? (tgt ? (const void*)&k_ticks<Sys, real, true, true, true> : (const void*)&k_ticks<Sys, real, true, false, true>)
-                               : (tgt ? (const void*)&k_ticks<Sys, real, false, true, true> : (const void*)&k_ticks<Sys, real, false, false, true>);
-      HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    }
-    if (generic && tgt)
-      RCG_TICKS(true, true);
-    else if (generic)
-      RCG_TICKS(true, false);
-    else if (tgt)
-      RCG_TICKS(false, true);
-    else
-      RCG_TICKS(false, false);
-#undef RCG_TICKS
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, A.G);
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    // (a generated grid asks for no LDS: L.lds == 0)
+    return with_bools(
+        [&](auto STR, auto GEN, auto TGT) {
+          auto fn = k_ticks<Sys, real, GEN(), TGT(), STR()>;
+          if (L.lds > 64 * 1024)
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.lds));
+          RCG_LAUNCH(h, fn, L.grid, L.block, L.lds, A, P);
+          return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, A.G);
+        },
+        L.stream, L.generic, L.tgt);
   });
 }
 
@@ -1215,52 +1138,19 @@ static int ticks_mem_plan(rcg_handle* h, int DU, bool sys_tgt, bool any_tgt, int
   memset(&M, 0, sizeof M);
   ActorArgs<real>& A = M.A;
   A.cand = (const real*)cand;  // nullptr: the generated grid
-  A.obs = (const real*)h->f[RCG_FIELD_STATE];
-  A.obs_x = 1;  // the kernel is handed the handle's STATE: y_0 = out(STATE), the identity for the built-ins (actor_plan)
-  A.state_sys = (const real*)h->f[(c.flags & RCG_FLAG_REF_LAG) ? RCG_FIELD_STATE_PREV : RCG_FIELD_STATE];
-  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  A.w = (const real*)h->f[RCG_FIELD_W_CRITIC];
+  // a tick on the handle's own fields: no caller's observation, state or weights (nothing to refuse)
+  (void)decision_inputs(h, "rcg_control_ticks", nullptr, nullptr, nullptr, true, nullptr, A, A.step_idx);
   A.action_out = (real*)h->f[RCG_FIELD_ACTION];
   A.best_J = (real*)h->f[RCG_FIELD_BEST_J];
   A.best_idx = (int32_t*)h->f[RCG_FIELD_BEST_IDX];
-  A.accum = !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
-  A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
-  A.K = K;
-  if (K >= 64) {
-    A.Kp = 64;
-    A.G = 1;
-    A.n_tiles = (K + 63) / 64;
-  } else {
-    int kp = 1;
-    while (kp < K) kp <<= 1;
-    A.Kp = kp;
-    A.G = 64 / kp;
-    A.n_tiles = 1;
-  }
-  A.grid_g = cand ? 0 : (DU == 1 ? K : (int)std::floor(std::sqrt((double)K) + 1e-9));
-  A.no_multi = dev_knobs().no_gen_multi ? 1 : 0;
+  tile_candidates(A, K);
+  A.grid_g = cand ? 0 : grid_side(DU, K);
   const size_t row_bytes = (size_t)c.n_actor * DU * sizeof(real);
   A.vec_ok = (cand && row_bytes % 16 == 0 && ((uintptr_t)cand % 16) == 0) ? 1 : 0;
   const size_t lds = cand ? (size_t)4 * 64 * row_bytes : 0;  // four waves, a 64-row tile each
   if (lds > (size_t)64 * 1024)
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_n: rows of %zu bytes do not fit the persistent kernel's tiles", row_bytes);
-  FitArgs<real>& F = M.F;
-  F.w_critic = (real*)h->f[RCG_FIELD_W_CRITIC];
-  F.w_prev = (real*)h->f[RCG_FIELD_W_PREV];
-  F.obs_buf = (real*)h->f[RCG_FIELD_OBS_BUF];
-  F.act_buf = (real*)h->f[RCG_FIELD_ACT_BUF];
-  F.wcfg = reinterpret_cast<const double*>((unsigned char*)h->d_const + kConstW);
-  F.do_sim = 1;
-  F.do_push = 1;
-  F.state = (const real*)h->f[RCG_FIELD_STATE];
-  F.action = (const real*)h->f[RCG_FIELD_ACTION];
-  F.sim.state = (real*)h->f[RCG_FIELD_STATE];
-  F.sim.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
-  F.sim.action = (const real*)h->f[RCG_FIELD_ACTION];
-  F.sim.pars_env = (const real*)h->f[RCG_FIELD_PARS];
-  F.sim.accum = (real*)h->f[RCG_FIELD_ACCUM];
-  F.sim.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
-  F.sim.n_sub = c.substeps_per_tick;
+  fit_args<real>(h, M.F, 1, 1, 0, c.substeps_per_tick);
   M.T = T;
   M.tick0 = (int)h->tick_count;
   M.every = c.critic_every_ticks > 1 ? c.critic_every_ticks : 1;
@@ -1282,42 +1172,26 @@ static int ticks_mem_plan(rcg_handle* h, int DU, bool sys_tgt, bool any_tgt, int
 // a caller's tensor.
 template <typename Sys>
 int op_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
-  const rcg_cfg& c = h->cfg;
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     const KParams<real>& P = params<real>(h);
     TicksMemArgs<real> M;
     TicksMemPlan L;
-    {
-      const int rc = ticks_mem_plan<real>(h, Sys::DU, Sys::TGT, false, T, K, cand, M, L);
-      if (rc) return rc;
-    }
-    const int m = c.n_critic - 1;
-    const size_t lds = L.lds;
-    const dim3 grid = L.grid, block = L.block;
+    const int rc = ticks_mem_plan<real>(h, Sys::DU, Sys::TGT, false, T, K, cand, M, L);
+    if (rc) return rc;
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
-#define RCG_TM(CS)                                                                                              \
-  do {                                                                                                          \
-    constexpr bool ml_ = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value >= kFitLanesMinDc;                          \
-    if (m <= 3 && cand)                                                                                         \
-      RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS, 3, Sys::TGT, ml_, true>), grid, block, lds, M, h->p64, P);      \
-    else if (m <= 3)                                                                                            \
-      RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS, 3, Sys::TGT, ml_, false>), grid, block, 0, M, h->p64, P);       \
-    else if (cand)                                                                                              \
-      RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS, kFitMaxRows, Sys::TGT, false, true>), grid, block, lds, M, h->p64, P); \
-    else                                                                                                        \
-      RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS, kFitMaxRows, Sys::TGT>), grid, block, 0, M, h->p64, P);        \
-  } while (0)
-    switch (c.critic_struct) {
-      case RCG_CRITIC_QUAD_LIN: RCG_TM(RCG_CRITIC_QUAD_LIN); break;
-      case RCG_CRITIC_QUADRATIC: RCG_TM(RCG_CRITIC_QUADRATIC); break;
-      case RCG_CRITIC_QUAD_NOMIX: RCG_TM(RCG_CRITIC_QUAD_NOMIX); break;
-      default: RCG_TM(RCG_CRITIC_QUAD_MIX); break;
-    }
-#undef RCG_TM
-    note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, M.A.G);
-    HIPCHK(h, hipGetLastError());
-    return (int)RCG_OK;
+    // (instances: the system's own TGT; the four-lane fit exactly for the structures with kFitLanesMinDc weights or more at
+    // up to 3 TD rows - what L.ml says -, never for more rows; a generated grid asks for no LDS)
+    with_critic(L.cs, [&](auto CS) {
+      constexpr bool ml_ = CriticDim<CS(), sys_dy<Sys>(), Sys::DU>::value >= kFitLanesMinDc;
+      if (L.maxm == 3)
+        with_bools([&](auto STR) { RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS(), 3, Sys::TGT, ml_, STR()>), L.grid, L.block, L.lds, M, h->p64, P); },
+                   L.stream);
+      else
+        with_bools([&](auto STR) { RCG_LAUNCH(h, (k_ticks_mem<Sys, real, CS(), kFitMaxRows, Sys::TGT, false, STR()>), L.grid, L.block, L.lds, M, h->p64, P); },
+                   L.stream);
+    });
+    return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_TICKS, L.variant, M.A.G);
   });
 }
 
@@ -1345,9 +1219,7 @@ static int op_nominal(rcg_handle* h, const void* obs, void* action, void* lyap, 
       A.clip = clip;
       ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
       RCG_LAUNCH(h, (k_nominal<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, A, params<real>(h));
-      note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 0, 64);
-      HIPCHK(h, hipGetLastError());
-      return (int)RCG_OK;
+      return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 0, 64);
     });
   }
 }
