@@ -27,7 +27,9 @@
 extern "C" {
 #endif
 
-#define RCG_VERSION 125 /* 124 + rcg_system_has_ticks (T ticks per launch for a registered policy with TICKS = true) */
+#define RCG_VERSION 125 /* 124 + rcg_system_has_ticks (T ticks per launch for a registered policy with TICKS = true).
+                           rcg_system_disturb_dim (the disturbance model of a registered policy with DD / disturb) was added
+                           WITHOUT a version bump: a caller detects the feature by the symbol itself */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -87,7 +89,8 @@ typedef enum rcg_where { RCG_HOST = 0, RCG_DEVICE = 1 } rcg_where;
                                             (reference loop order, presets/main_3wrobot.py:425-428)    */
 #define RCG_FLAG_ACCUM_EVERY_SUBSTEP 0x8 /* upd_accum_obj every sim step (controllers.py:1093 quirk)    */
 #define RCG_FLAG_NO_CLIP 0x10            /* ctrl_bnds all zero <=> unconstrained (systems.py:241)       */
-#define RCG_FLAG_DISTURB 0x20            /* System(is_disturb=1): full state [state, disturb] (systems.py:140-145) */
+#define RCG_FLAG_DISTURB 0x20            /* System(is_disturb=1): full state [state, disturb] (systems.py:140-145); a
+                                            registered system: only a policy with DD / disturb (rcg_register_system)   */
 
 /* per-env tensors owned by the handle (rcg_set_field / rcg_get_field) */
 typedef enum rcg_field {
@@ -108,7 +111,8 @@ typedef enum rcg_field {
   RCG_FIELD_ACT_BUF = 14,    /* [buffer_size][du][B] real                                         */
   RCG_FIELD_RETURNS = 15,    /* [B]      real    accum_obj of the last finished episode           */
   RCG_FIELD_ACTION_SQN = 16, /* [B][N][du] real  last optimised action sequence, one row per env  */
-  RCG_FIELD_DISTURB = 17,    /* [dd][B] real  disturbance part of the full state (RCG_FLAG_DISTURB); dd = 2, 2, 1 */
+  RCG_FIELD_DISTURB = 17,    /* [dd][B] real  disturbance part of the full state (RCG_FLAG_DISTURB); dd = 2, 2, 1 for the
+                                built-in systems, a registered policy's DD (rcg_system_disturb_dim) */
   RCG_FIELD_SUBSTEP_IDX = 18, /* [B] int32  simulation substeps since the episode began: noise counter word 3  */
   RCG_FIELD_COUNT_ = 19
 } rcg_field;
@@ -190,10 +194,10 @@ int rcg_device_count(void);
  * (seconds; no device needed); a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error(NULL).  The same name and
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
- * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  rcg_create
- * refuses RCG_FLAG_DISTURB; the nominal controllers, rcg_rhs_full and rcg_loop_step - and, without SEARCH (below),
- * rcg_actor_search and rcg_control_tick_search, without TICKS (below) rcg_control_ticks - return RCG_ERR_UNSUPPORTED with the
- * handle untouched.
+ * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  The nominal
+ * controllers and rcg_loop_step - and, without SEARCH (below), rcg_actor_search and rcg_control_tick_search, without TICKS
+ * (below) rcg_control_ticks, without the disturbance model (below) rcg_create with RCG_FLAG_DISTURB - return
+ * RCG_ERR_UNSUPPORTED with the handle untouched.
  * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
  * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
  * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
@@ -215,7 +219,22 @@ int rcg_device_count(void);
  * has an output map.  The one instance a handle needs is compiled as a program of its own the first time it is asked for,
  * before the call enqueues anything (a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error and the handle
  * untouched); the opt-in adds nothing to the registration itself.  Without TICKS rcg_control_ticks is RCG_ERR_UNSUPPORTED and
- * rcg_control_tick_n loops single ticks. */
+ * rcg_control_tick_n loops single ticks.
+ * The disturbance model (System(is_disturb=1), systems.py:140-145): a policy opts in with the two members
+ *   static constexpr int DD = 1;   // dim_disturb: 1 or 2 (RCG_ERR_UNSUPPORTED otherwise)
+ *   template <typename real>
+ *   __device__ __forceinline__ static void disturb(const Pre<real>& q, const real* x, const real* u, const real* w, real* d);
+ * disturb is called right after rhs<real, false>(q, x, u, d) with the clipped action u and the disturbance state w[DD], and adds
+ * to / overwrites entries of d: the reference's _state_dyn(t, state, action, disturb).  One member without the other is
+ * RCG_ERR_BAD_ARG with a message that names the missing one.  The disturbance's own dynamics are the reference's first-order
+ * filter dq_k/dt = -tau_k (q_k + sigma_k (xi_k + mu_k)) with the noise of rcg_cfg (below: drawn once per RK4 substep and env).
+ * rcg_create then accepts RCG_FLAG_DISTURB for the system: rcg_sim_step and the env step of every tick (MPC, RQL / SQL, search,
+ * optimiser) run on k_sim_dist, rcg_rhs_full on k_rhs_full, rcg_control_ticks (MPC, with TICKS) on k_ticks' disturbed branch -
+ * the kernels the built-in systems run; rcg_disturb_noise, RCG_FIELD_DISTURB ([DD][B]) / RCG_FIELD_SUBSTEP_IDX and
+ * rcg_episode_reset work as for them.  The rollouts of a decision stay disturbance-free, as in the reference.  The two kernels
+ * are compiled as one program per element type the first time such a handle needs it, before the call enqueues anything; the
+ * opt-in adds nothing to the registration itself.  RQL / SQL T ticks per launch, rcg_loop_step, the two-halves tick and the
+ * nominal controllers are refused under the disturbance model, as for the built-in systems. */
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
@@ -235,9 +254,13 @@ int rcg_system_has_search(int32_t sys_id, int32_t* has_search);
 /* whether a system runs T ticks per launch (rcg_control_ticks, the persistent path of rcg_control_tick_n): 1 for the built-in
  * ones and for a registered policy with TICKS = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system. */
 int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks);
+/* dim_disturb of a system's disturbance model (RCG_FLAG_DISTURB; the rows of RCG_FIELD_DISTURB): 2, 2, 1 for the built-in
+ * systems, DD for a registered policy with the `disturb` member, 0 for one without (rcg_create refuses RCG_FLAG_DISTURB for
+ * it).  RCG_ERR_BAD_ARG for an id that names no system and for dd == NULL.  (Added without a version bump, RCG_VERSION.) */
+int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd);
 /* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
  * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs,
- * k_actor_search instances, k_ticks / k_ticks_mem instances).  Writes at
+ * k_actor_search instances, k_ticks / k_ticks_mem instances, disturb programs).  Writes at
  * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
 int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 

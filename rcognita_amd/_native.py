@@ -26,7 +26,7 @@ F32, F64 = 0, 1
 HOST, DEVICE = 0, 1
 FLAG_HAS_TARGET, FLAG_PER_ENV_PARS, FLAG_REF_LAG, FLAG_ACCUM_EVERY_SUBSTEP, FLAG_NO_CLIP = 1, 2, 4, 8, 16
 FLAG_DISTURB = 32
-DIM_DISTURB = {0: 2, 1: 2, 2: 1}  # sys_id -> dim_disturb (presets/main_*.py)
+DIM_DISTURB = {0: 2, 1: 2, 2: 1}  # sys_id -> dim_disturb (presets/main_*.py; + registered systems whose policy has `disturb`)
 
 (FIELD_STATE, FIELD_ACTION, FIELD_ACCUM, FIELD_STEP_IDX, FIELD_EPISODE_IDX, FIELD_STATUS, FIELD_PARS,
  FIELD_STATE_INIT, FIELD_STATE_PREV, FIELD_BEST_J, FIELD_BEST_IDX, FIELD_W_CRITIC, FIELD_W_PREV, FIELD_OBS_BUF,
@@ -55,7 +55,7 @@ SYMBOLS = [
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
     "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit", "rcg_last_launch_zero_w", "rcg_system_has_search",
-    "rcg_system_has_ticks",
+    "rcg_system_has_ticks", "rcg_system_disturb_dim",
 ]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
@@ -192,6 +192,7 @@ def lib():
         "rcg_system_has_critic": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_system_has_search": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_system_has_ticks": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_system_disturb_dim": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_critic_fit": (C.c_int, [vp]),
         "rcg_system_programs": (C.c_int, [i32, C.c_char_p, i64, C.POINTER(i64)]),
     }
@@ -217,12 +218,13 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks"}``: the id to put in ``rcg_cfg.sys_id``
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks", "dd"}``: the id to put in ``rcg_cfg.sys_id``
     (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
     optimiser), its dim_output ``DY``, whether it defines the output map ``out`` and its adjoint ``out_jac_T``, and whether it opts
     in to the critic kernels (``CRITIC``: RQL / SQL), to the device search (``SEARCH``: rcg_actor_search) and to T ticks per launch
-    (``TICKS``: rcg_control_ticks, the persistent path of rcg_control_tick_n).  ``SYS_DIMS``
-    (``(ds, du, np)``) and ``SYS_DY`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
+    (``TICKS``: rcg_control_ticks, the persistent path of rcg_control_tick_n), and ``dd``: its dim_disturb ``DD`` when it has the
+    ``disturb`` member (the disturbance model: ``RCG_FLAG_DISTURB`` handles), else 0.  ``SYS_DIMS``
+    (``(ds, du, np)``), ``SYS_DY`` and - with ``disturb`` - ``DIM_DISTURB`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
     the dimension limits)."""
     import time
 
@@ -245,9 +247,13 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     check(L.rcg_system_has_search(sid.value, C.byref(srch)))
     tck = C.c_int32(0)
     check(L.rcg_system_has_ticks(sid.value, C.byref(tck)))
+    dd = C.c_int32(0)
+    check(L.rcg_system_disturb_dim(sid.value, C.byref(dd)))
+    if dd.value > 0:
+        DIM_DISTURB[sid.value] = dd.value
     return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
             "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value),
-            "has_critic": bool(crit.value), "has_search": bool(srch.value), "has_ticks": bool(tck.value)}
+            "has_critic": bool(crit.value), "has_search": bool(srch.value), "has_ticks": bool(tck.value), "dd": dd.value}
 
 
 def system_programs(sys_id: int) -> list:

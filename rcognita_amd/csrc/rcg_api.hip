@@ -104,6 +104,7 @@ static bool system_dims(int sys_id, RtcDims* d, const RtcSystem** rtc = nullptr)
     d->du = kDims[sys_id][1];
     d->np = kDims[sys_id][2];
     d->has_jac = d->has_critic = d->has_search = d->has_ticks = true;
+    d->dd = sys_id == RCG_SYS_2TANK ? 1 : 2;  // dim_disturb of the presets (main_*.py dim_disturb)
     return true;
   }
   const RtcSystem* S = sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(sys_id, d) : nullptr;
@@ -233,6 +234,14 @@ int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks) {
   return RCG_OK;
 }
 
+int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_disturb_dim: bad sys_id %d", sys_id);
+  if (!dd) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_disturb_dim: null argument");
+  *dd = d.dd;
+  return RCG_OK;
+}
+
 int rcg_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -265,8 +274,10 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   if (dim_critic(cfg->critic_struct, rd.dy, du) > RCG_MAX_DC)
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: dim_critic %d (dim_output %d, dim_input %d) beyond the limit %d",
                     dim_critic(cfg->critic_struct, rd.dy, du), rd.dy, du, RCG_MAX_DC);
-  if (rtc && (cfg->flags & RCG_FLAG_DISTURB))
-    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_create: a system registered at run time has no disturbance model");
+  // (a policy opts in to the disturbance model with the members DD and `disturb`, rcg.h)
+  if (rtc && (cfg->flags & RCG_FLAG_DISTURB) && rd.dd < 1)
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED,
+                    "rcg_create: a system registered at run time has no disturbance model unless its policy defines DD and disturb");
   // (the reference's horizon is unbounded, controllers.py:965.  Rows of up to RCG_MAX_ROW reals are staged in LDS tiles; longer
   // ones are walked straight from HBM by the generic decision kernel, and the optimiser / search keep their per-wave LDS
   // budget: they refuse - before touching anything - a horizon their working set does not fit, rcg.h)
@@ -297,6 +308,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->np = np;
   h->rtc_has_out = rtc && rd.has_out;
   h->rtc_has_ticks = rtc && rd.has_ticks;
+  h->dd = rd.dd;
   h->dy = rd.dy;  // R1 / R2 are (dy + du)^2 and the target has dy entries
   h->nchi = h->dy + du;
   h->dc = dim_critic(cfg->critic_struct, h->dy, du);  // the critic's regressor is over [y, u] (controllers.py:1192-1214)
@@ -386,7 +398,7 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   h->fbytes[RCG_FIELD_BEST_IDX] = B * 4;
   h->fbytes[RCG_FIELD_RETURNS] = B * e;
   h->fbytes[RCG_FIELD_ACTION_SQN] = (size_t)cfg->n_actor * du * B * e;
-  const int dd = cfg->sys_id == RCG_SYS_2TANK ? 1 : 2;  // dim_disturb of the presets (main_*.py dim_disturb)
+  const int dd = h->dd;  // dim_disturb: the presets' (main_*.py dim_disturb), a registered policy's DD
   if (cfg->flags & RCG_FLAG_DISTURB) {
     h->fbytes[RCG_FIELD_DISTURB] = dd * B * e;
     h->fbytes[RCG_FIELD_SUBSTEP_IDX] = B * 4;
@@ -1296,7 +1308,7 @@ int rcg_episode_reset(rcg_handle* h) {
                        (float)h->cfg.action_init[1], B);
   HIPCHK(h, hipGetLastError());
   if (h->cfg.flags & RCG_FLAG_DISTURB) {  // disturbance back to disturb_init, noise counter word 3 back to 0
-    const int dd = h->cfg.sys_id == RCG_SYS_2TANK ? 1 : 2;
+    const int dd = h->dd;
     const int rc = h->cfg.dtype == RCG_F64 ? fill_rows<double>(h, h->f[RCG_FIELD_DISTURB], dd, h->cfg.disturb_init)
                                            : fill_rows<float>(h, h->f[RCG_FIELD_DISTURB], dd, h->cfg.disturb_init);
     if (rc) return rc;

@@ -13,6 +13,10 @@
 #pragma once
 #include "rcg_kernels.hpp"
 
+// (a unit generated for a system registered at run time specialises Disturb<RcgRtcSys> wherever this header is part of it:
+// rcg_rtc.hip::unit_source)
+#define RCG_DISTURB_HPP 1
+
 namespace rcg {
 
 struct PhiloxOut {
@@ -65,7 +69,9 @@ struct DisturbPars {
   int64_t env_id_base;
 };
 
-// how the disturbance enters _state_dyn, and its dimension
+// how the disturbance enters _state_dyn, and its dimension: apply(pre, x, u, q, d) runs right after Sys::rhs(pre, x, u, d) with
+// the state x, the clipped action u and the disturbance q[DD], and adds to / overwrites entries of d.  (The built-in systems'
+// do not read x; a policy registered at run time may: its `disturb` member, include/rcg.h.)
 template <typename Sys>
 struct Disturb;
 template <>
@@ -73,7 +79,8 @@ struct Disturb<Sys3WRobot> {
   static constexpr int DD = 2;
   static constexpr bool inert = false;
   template <typename real>
-  __device__ __forceinline__ static void apply(const Sys3WRobot::Pre<real>& p, const real* u, const real* q, real* d) {
+  __device__ __forceinline__ static void apply(const Sys3WRobot::Pre<real>& p, const real*, const real* u, const real* q,
+                                                real* d) {
     d[3] = p.inv_m * (u[0] + q[0]);  // 1/m * (action[0] + disturb[0])
     d[4] = p.inv_I * (u[1] + q[1]);
   }
@@ -83,7 +90,8 @@ struct Disturb<Sys3WRobotNI> {
   static constexpr int DD = 2;
   static constexpr bool inert = false;
   template <typename real>
-  __device__ __forceinline__ static void apply(const Sys3WRobotNI::Pre<real>&, const real*, const real* q, real* d) {
+  __device__ __forceinline__ static void apply(const Sys3WRobotNI::Pre<real>&, const real*, const real*, const real* q,
+                                                real* d) {
     d[0] += q[0];
     d[1] += q[0];  // the reference adds disturb[0] to both (systems.py:374-375)
     d[2] += q[1];
@@ -94,7 +102,7 @@ struct Disturb<Sys2Tank> {
   static constexpr int DD = 1;
   static constexpr bool inert = true;  // _disturb_dyn returns zeros and _state_dyn ignores it
   template <typename real>
-  __device__ __forceinline__ static void apply(const Sys2Tank::Pre<real>&, const real*, const real*, real*) {}
+  __device__ __forceinline__ static void apply(const Sys2Tank::Pre<real>&, const real*, const real*, const real*, real*) {}
 };
 
 // closed_loop_rhs on the full state with the (already clipped) action and a given noise value
@@ -103,7 +111,7 @@ __device__ __forceinline__ void rhs_full(const typename Sys::template Pre<real>&
                                          const real* q, const real* u, const real* xi, real* dx, real* dq) {
   constexpr int DD = Disturb<Sys>::DD;
   Sys::template rhs<real>(pre, x, u, dx);
-  Disturb<Sys>::template apply<real>(pre, u, q, dx);
+  Disturb<Sys>::template apply<real>(pre, x, u, q, dx);
 #pragma unroll
   for (int k = 0; k < DD; ++k)
     dq[k] = Disturb<Sys>::inert ? (real)0
@@ -171,7 +179,7 @@ __device__ __forceinline__ bool env_substeps_dist(const KParams<real>& P, const 
                                                   const typename Sys::template Pre<real>& pre, int n_sub, int64_t env_id,
                                                   int32_t ep, real* x, real* xp, real* q, int32_t& sub, const real* a_held,
                                                   uint32_t& st, real& accum) {
-  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU, DD = Disturb<Sys>::DD;
+  constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = sys_dy<Sys>() + DU, DD = Disturb<Sys>::DD;
   if (st & 1u) return false;  // frozen env
   real u[DU], xn[DS], xq[DS], qn[DD];
 #pragma unroll
@@ -191,8 +199,9 @@ __device__ __forceinline__ bool env_substeps_dist(const KParams<real>& P, const 
     rk4_step_full<Sys, real>(pre, D, xn, qn, u, xi, P.dt_sim);
     subn += 1;
     if (P.accum_every_substep) {
-      real chi[NCHI];
-      make_chi<DS, DU, TGT, real>(P, xn, u, chi);
+      real chi[NCHI], yn[sys_dy<Sys>()];  // charged at y = out(x), as env_substeps does (the state itself without an output map)
+      sys_out<Sys, real, false>(pre, xn, yn);
+      make_chi<sys_dy<Sys>(), DU, TGT, real>(P, yn, u, chi);
       acc = fma_r(stage_any<NCHI, real>(P, chi), P.sampling_time, acc);
     }
   }

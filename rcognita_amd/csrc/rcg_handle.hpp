@@ -22,6 +22,7 @@ struct rcg_handle {
   int ds, du, np, dc, nchi;
   int dy;      // dim_output: ds, or the DY of a registered system with an output map (nchi = dy + du)
   bool rtc_has_out;  // a registered system with an output map (rcg_out launches k_out)
+  int dd;      // dim_disturb: 2 / 2 / 1 for the built-ins, a registered policy's DD (0: it has no `disturb` member)
   bool rtc_has_ticks;  // a registered system whose policy opts in with TICKS (k_ticks / k_ticks_mem compiled on first use)
   size_t esz;  // sizeof(real)
   hipStream_t stream;
@@ -277,6 +278,7 @@ struct RtcDims {  // (`RtcDims d;` is the description of nothing)
   bool has_critic = false;   // the policy opts in to the critic kernels (static constexpr bool CRITIC = true): RQL / SQL handles
   bool has_search = false;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
   bool has_ticks = false;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
+  int dd = 0;                // dim_disturb: the policy's DD when it has the `disturb` member (RCG_FLAG_DISTURB handles), else 0
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])

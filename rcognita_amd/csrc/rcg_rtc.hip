@@ -18,12 +18,19 @@
 //                    search_plan picks for a handle (<name>_search.hip);
 //                    for a policy that opts in with `static constexpr bool TICKS = true`, the k_ticks instance ticks_plan picks
 //                    (<name>_ticks.hip) and the k_ticks_mem instance ticks_mem_plan picks (<name>_ticks_mem.hip);
+//                    for a policy that opts in to the disturbance model with `static constexpr int DD` and the member `disturb`,
+//                    the disturb program of an element type, the first time a handle with RCG_FLAG_DISTURB steps an env or asks
+//                    for rcg_rhs_full: k_sim_dist (with and without a target) and k_rhs_full (<name>_disturb.hip).  The adapter
+//                    generates Disturb<RcgRtcSys> from the two members in every unit that includes rcg_disturb.hpp, so the
+//                    k_ticks instances of such a policy run the disturbed env step too (TicksArgs::dist);
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan / ticks_plan /
 // ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is
 // not compiled is refused with RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC
 // (rcg_create refuses RQL / SQL for it), the device search of a policy without SEARCH, T ticks per launch of a policy without
-// TICKS, the nominal controllers and rcg_loop_step (rcg_create refuses the disturbance model for these systems).  One mutex
+// TICKS, the nominal controllers and rcg_loop_step; rcg_create refuses the disturbance model for a policy without `disturb`, and
+// under it RQL / SQL through k_ticks_mem, the two-halves tick and the fused env step stay refused or unfused as for the built-in
+// systems.  One mutex
 // guards the registry and every cache, the compiler runs outside it, and a handle keeps the functions it has resolved; nothing
 // is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
@@ -87,21 +94,28 @@ bool is_identifier(const char* s) {
 // The generated unit: the kernel headers of its flavour (Core: the probe, the core programs and the k_actor_dma instances), the
 // policy (its own file name and line numbers in hipRTC's log), the adapter that supplies the optional members and the checks of
 // the declared dimensions.
-enum class Unit { Core, Critic, Search, Ticks };
+enum class Unit { Core, Critic, Search, Ticks, Disturb };
 std::string unit_source(const RtcSystem& S, Unit unit) {
   const bool critic = unit == Unit::Critic, search = unit == Unit::Search, ticks = unit == Unit::Ticks;
-  char dims[1536];
+  const bool disturb = unit == Unit::Disturb;
+  char dims[2560];
   snprintf(dims, sizeof dims,
            "static_assert(RcgRtcSys::DS == %d, \"rcg_register_system: %s::DS differs from the declared ds\");\n"
            "static_assert(RcgRtcSys::DU == %d, \"rcg_register_system: %s::DU differs from the declared du\");\n"
            "static_assert(RcgRtcSys::NP == %d, \"rcg_register_system: %s::NP differs from the declared np\");\n"
            "static_assert(RcgRtcSys::HAS_OUT || RcgRtcSys::DY == RcgRtcSys::DS, \"rcg_register_system: %s::DY differs from DS "
-           "but %s defines no out (without an output map the observation is the state)\");\n",
-           S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str());
+           "but %s defines no out (without an output map the observation is the state)\");\n"
+           "static_assert(!rtc::dd<%s>::has || rtc::dist<%s>::v, \"rcg_register_system: %s defines DD but no disturb member "
+           "(the disturbance model needs both: template <typename real> static void disturb(q, x, u, w, d))\");\n"
+           "static_assert(!rtc::dist<%s>::v || rtc::dd<%s>::has, \"rcg_register_system: %s defines disturb but no DD member "
+           "(the disturbance model needs both: static constexpr int DD = 1 or 2)\");\n",
+           S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str(),
+           S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str());
   const std::string& N = S.name;
   return std::string(critic ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_critic_fit_gen.hpp\"\n" : "") +
          (search ? "#include \"rcg_search.hpp\"\n" : "") +
          (ticks ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_ticks.hpp\"\n" : "") +
+         (disturb ? "#include \"rcg_disturb.hpp\"\n" : "") +
          "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
@@ -127,8 +141,13 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "template <class S> struct srch<S, void_t<decltype(S::SEARCH)>> { static constexpr bool v = S::SEARCH; };\n"
          "template <class S, class = void> struct tck { static constexpr bool v = false; };\n"
          "template <class S> struct tck<S, void_t<decltype(S::TICKS)>> { static constexpr bool v = S::TICKS; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW> __global__ void "
-         "k_rtc_probe() {}\n"
+         "template <class S, class = void> struct dd { static constexpr bool has = false; static constexpr int v = 0; };\n"
+         "template <class S> struct dd<S, void_t<decltype(S::DD)>> { static constexpr bool has = true; static constexpr int v = S::DD; };\n"
+         "template <class S, class = void> struct dist { static constexpr bool v = false; };\n"
+         "template <class S> struct dist<S, void_t<decltype(&S::template disturb<float>)>> { static constexpr bool v = true; };\n"
+         "template <class S> struct ddv { static constexpr int v = dist<S>::v ? (dd<S>::v == 0 ? -1 : dd<S>::v) : 0; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD> __global__ "
+         "void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -137,15 +156,30 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "  static constexpr bool HAS_OUT = rtc::out<" + N + ">::v;\n"
          "  static constexpr int DY = rtc::dy<" + N + ">::v;\n"
          "};\n" +
-         // k_ticks names Disturb<Sys>: an inert one, shaped like Disturb<Sys2Tank> (rcg_create refuses the disturbance model for
-         // a registered system, so TicksArgs::dist is 0 and env_substeps_dist never runs)
-         (ticks ? "template <> struct Disturb<RcgRtcSys> {\n"
-                  "  static constexpr int DD = 1;\n"
-                  "  static constexpr bool inert = true;\n"
-                  "  template <typename real>\n"
-                  "  __device__ __forceinline__ static void apply(const RcgRtcSys::Pre<real>&, const real*, const real*, real*) {}\n"
-                  "};\n"
-                : "") +
+         // Disturb<RcgRtcSys>, in every unit that includes rcg_disturb.hpp (k_ticks and k_actor_search name it): the policy's DD
+         // and `disturb`, or - a policy that does not opt in - an inert one shaped like Disturb<Sys2Tank> (rcg_create refuses the
+         // disturbance model for it, so TicksArgs::dist is 0 and env_substeps_dist never runs)
+         "#ifdef RCG_DISTURB_HPP\n"
+         "namespace rtc {\n"
+         "template <class S, bool ON> struct disturb_of {\n"
+         "  static constexpr int DD = 1;\n"
+         "  static constexpr bool inert = true;\n"
+         "  template <typename real>\n"
+         "  __device__ __forceinline__ static void apply(const typename S::template Pre<real>&, const real*, const real*, const real*,\n"
+         "                                               real*) {}\n"
+         "};\n"
+         "template <class S> struct disturb_of<S, true> {\n"
+         "  static constexpr int DD = S::DD;\n"
+         "  static constexpr bool inert = false;\n"
+         "  template <typename real>\n"
+         "  __device__ __forceinline__ static void apply(const typename S::template Pre<real>& q, const real* x, const real* u,\n"
+         "                                               const real* w, real* d) {\n"
+         "    S::template disturb<real>(q, x, u, w, d);\n"
+         "  }\n"
+         "};\n"
+         "}  // namespace rtc\n"
+         "template <> struct Disturb<RcgRtcSys> : rtc::disturb_of<" + N + ", (rtc::ddv<" + N + ">::v > 0)> {};\n"
+         "#endif\n" +
          dims + "}  // namespace rcg\n";
 }
 
@@ -213,6 +247,14 @@ std::string expr_out() {
 template <typename real>
 std::string expr_sim(bool tgt) {
   return std::string("rcg::k_sim<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ">";
+}
+template <typename real>
+std::string expr_sim_dist(bool tgt) {
+  return std::string("rcg::k_sim_dist<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ">";
+}
+template <typename real>
+std::string expr_rhs_full() {
+  return std::string("rcg::k_rhs_full<") + kSysExpr + ", " + real_name<real>() + ">";
 }
 template <typename real>
 std::string expr_actor(bool gen, bool tgt, bool str, bool direct) {
@@ -400,6 +442,16 @@ int search_function(rcg_handle* h, const SearchPlan& L, hipFunction_t* fn) {
   return lazy_function(h, Unit::Search, "search", {expr_search<real>(L.generic, L.tgt, L.nc)}, 0, fn);
 }
 
+// The disturb program of an element type - k_sim_dist without and with a target, k_rhs_full - for a policy with DD / disturb
+// (rcg_create has refused RCG_FLAG_DISTURB for any other); `want`: which of the three
+enum { DISTURB_SIM = 0, DISTURB_SIM_TGT = 1, DISTURB_RHS_FULL = 2 };
+template <typename real>
+int disturb_function(rcg_handle* h, int want, hipFunction_t* fn) {
+  if (h->rtc->dims.dd < 1) return RCG_ERR_UNSUPPORTED;  // (the callers refuse by name first)
+  const std::vector<std::string> exprs{expr_sim_dist<real>(false), expr_sim_dist<real>(true), expr_rhs_full<real>()};
+  return lazy_function(h, Unit::Disturb, "disturb", exprs, want, fn);
+}
+
 // a member of the table that the policy did not opt in to with `member` (CRITIC, SEARCH, TICKS)
 int refuse_opt_in(rcg_handle* h, const char* who, const char* member) {
   return rcg_fail(h, RCG_ERR_UNSUPPORTED,
@@ -462,14 +514,30 @@ int rtc_stage_obj(rcg_handle* h, const void* obs, const void* act, void* out, in
 }
 
 // the env step: k_sim (lane = env) at every batch size - k_sim_v, which the built-in light systems take from 2^18 envs on,
-// computes the same bits
+// computes the same bits; a handle with RCG_FLAG_DISTURB: k_sim_dist of the disturb program (compiled on first use, before the
+// launch: the env step is the first thing every caller enqueues), with the arguments op_sim_step fills
 template <typename real>
 int sim_step(rcg_handle* h, int32_t n_substeps) {
   hipFunction_t f;
-  int rc = core_function<real>(h, expr_sim<real>((h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0), &f);
-  if (rc) return rc;
+  const bool tgt = (h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0;
   SimArgs<real> A = sim_args<real>(h, n_substeps);
   KParams<real> P = params<real>(h);
+  if (h->cfg.flags & RCG_FLAG_DISTURB) {
+    int rc = disturb_function<real>(h, tgt ? DISTURB_SIM_TGT : DISTURB_SIM, &f);
+    if (rc) return rc;
+    SimDistArgs<real> D;
+    D.S = A;
+    D.disturb = (real*)h->f[RCG_FIELD_DISTURB];
+    D.substep_idx = (int32_t*)h->f[RCG_FIELD_SUBSTEP_IDX];
+    D.episode_idx = (const int32_t*)h->f[RCG_FIELD_EPISODE_IDX];
+    D.D = disturb_pars(h);
+    void* args[] = {&D, &P};
+    ProfScope prof_scope(h, RCG_KERNEL_SIM);
+    note_launch(h, RCG_KERNEL_SIM, RCG_KID_SIM_DIST, 0, 64);
+    return launch(h, f, dim3(blocks_for(h->cfg.batch)), dim3(256), 0, args);
+  }
+  int rc = core_function<real>(h, expr_sim<real>(tgt), &f);
+  if (rc) return rc;
   void* args[] = {&A, &P};
   ProfScope prof_scope(h, RCG_KERNEL_SIM);
   note_launch(h, RCG_KERNEL_SIM, RCG_KID_SIM, 0, 64);
@@ -697,8 +765,31 @@ int rtc_ticks_mem(rcg_handle* h, int32_t T, int32_t K, const void* cand) {
     return rc;
   });
 }
-int rtc_rhs_full(rcg_handle* h, const void*, const void*, const void*, const void*, void*, void*, void*, int32_t, int32_t) {
-  return refuse(h, "rcg_rhs_full");
+// closed_loop_rhs on the full state [state, disturb], noise given: op_rhs_full on the disturb program (rcg_rhs_full has checked
+// RCG_FLAG_DISTURB, which rcg_create grants a policy with DD / disturb only)
+int rtc_rhs_full(rcg_handle* h, const void* state, const void* disturb, const void* action, const void* xi, void* dstate,
+                 void* ddisturb, void* clipped, int32_t n, int32_t clip) {
+  if (h->rtc->dims.dd < 1) return refuse(h, "rcg_rhs_full");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = disturb_function<real>(h, DISTURB_RHS_FULL, &f);
+    if (rc) return rc;
+    const real* st = (const real*)state;
+    const real* q = (const real*)disturb;
+    const real* ac = (const real*)action;
+    const real* x = (const real*)xi;
+    real* ds = (real*)dstate;
+    real* dq = (real*)ddisturb;
+    real* cl = (real*)clipped;
+    const real* pe = pars_env_of<real>(h, n);
+    long nn = n;
+    int ci = clip;
+    DisturbPars D = disturb_pars(h);
+    KParams<real> P = params<real>(h);
+    void* args[] = {&st, &q, &ac, &x, &ds, &dq, &cl, &pe, &nn, &ci, &D, &P};
+    return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+  });
 }
 // The device search: op_search's plan (search_plan) on the program compiled for its instance.  The instance is resolved - and
 // compiled, the first time - before anything is enqueued.
@@ -733,20 +824,21 @@ int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, i
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW, DD> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E;
+// DD: the policy's DD when it has `disturb`, else 0)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
-                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET>";
+                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S, Unit::Core), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[9];
+  long v[10];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 9 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 10 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -757,7 +849,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 9) {
+  if (n != 10) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -770,6 +862,7 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.has_search = v[6] != 0;
   S.dims.has_ticks = v[7] != 0;
   S.zw = (unsigned)v[8];
+  S.dims.dd = (int)v[9];
   return RCG_OK;
 }
 
@@ -907,6 +1000,9 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   // refused by the adapter's static_assert above, with hipRTC's log)
   if (rc == RCG_OK && (S->dims.dy < 1 || S->dims.dy > RCG_MAX_DS))
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::DY = %d beyond 1 .. %d", name, S->dims.dy, RCG_MAX_DS);
+  // dim_disturb: DisturbPars, rcg_cfg::pars_disturb / disturb_init and the two normals of a Philox draw are sized for 2
+  if (rc == RCG_OK && (S->dims.dd < 0 || S->dims.dd > 2))
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::DD = %d beyond 1 .. 2", name, S->dims.dd);
   const std::string unit = unit_source(*S, Unit::Core);
   if (rc == RCG_OK) rc = compile(unit, S->name + "_f32.hip", core_exprs<float>(S->dims), &S->core[0], &log);
   if (rc == RCG_OK) rc = compile(unit, S->name + "_f64.hip", core_exprs<double>(S->dims), &S->core[1], &log);

@@ -113,7 +113,8 @@ class EngineConfig:
             flags |= N.FLAG_ACCUM_EVERY_SUBSTEP
         if self.is_disturb:
             if int(self.sys_id) not in N.DIM_DISTURB:
-                raise NotImplementedError("a system registered at run time has no disturbance model")
+                raise NotImplementedError("a system registered at run time has no disturbance model unless its policy has the "
+                                          "`disturb` member (and DD; INTEGRATION.md)")
             dd = N.DIM_DISTURB[int(self.sys_id)]
             flags |= N.FLAG_DISTURB
             if self.pars_disturb is None or len(self.pars_disturb) != 3:
@@ -243,7 +244,7 @@ class Engine:
         self._pool, self._pool_bytes = {}, 0  # free list of small scratch allocations, by capacity (DeviceArray)
         L = N.lib()
         self.ds, self.du, self.npar = N.SYS_DIMS[cfg.sys_id]
-        self.dd = N.DIM_DISTURB.get(int(cfg.sys_id), 0)  # (a system registered at run time has no disturbance model)
+        self.dd = N.DIM_DISTURB.get(int(cfg.sys_id), 0)  # (a registered system: its policy's DD, 0 without `disturb`)
         self.dy = N.sys_dy(cfg.sys_id)  # dim_output (a registered system's DY; the state's dimension otherwise)
         self.B = int(cfg.batch)
         self.N = int(cfg.Nactor)

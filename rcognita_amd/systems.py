@@ -15,8 +15,8 @@ Same class names, constructor signature and method names as the reference, so a 
 * your own system: instead of overriding ``_state_dyn`` in Python, a subclass sets ``hip_policy`` to the source of a policy
   struct in the shape of the built-ins (rcognita_amd/csrc/rcg_systems.hpp).  The class is compiled for the GPU on its first
   construction (``_native.register_system``) and runs the MPC path (RQL / SQL with ``CRITIC``, the device candidate search
-  with ``SEARCH``, T ticks per launch with ``TICKS`` in the policy - ``_hip_info["has_ticks"]``); INTEGRATION.md, "Your own
-  system".
+  with ``SEARCH``, T ticks per launch with ``TICKS`` in the policy - ``_hip_info["has_ticks"]`` -, ``is_disturb=1`` with the
+  members ``DD`` and ``disturb`` - ``_hip_info["dd"]``); INTEGRATION.md, "Your own system".
 """
 from __future__ import annotations
 
@@ -40,12 +40,13 @@ class System:
     def __init__(self, sys_type, dim_state, dim_input, dim_output, dim_disturb, pars=[], ctrl_bnds=[], is_dyn_ctrl=0,
                  is_disturb=0, pars_disturb=[], dtype="f64", device=0, seed=0):
         if type(self).hip_policy is not None:
-            if is_disturb:
-                raise NotImplementedError("a system compiled from hip_policy has no disturbance model (is_disturb=1)")
             if type(self).out is not System.out:
                 raise NotImplementedError("a system compiled from hip_policy cannot override `out` in Python (there is no CPU "
                                           "path): give the policy an `out` member (and DY, out_jac_T; INTEGRATION.md)")
             self._register_hip_policy(dim_state, dim_input, pars)
+            if is_disturb and not type(self)._hip_info["dd"]:
+                raise NotImplementedError("a system compiled from hip_policy has no disturbance model (is_disturb=1) unless the "
+                                          "policy has the `disturb` member (and DD; INTEGRATION.md)")
         if self._sys_id is None:
             raise NotImplementedError(
                 "only the built-in systems (Sys3WRobot, Sys3WRobotNI, Sys2Tank) run on the native path; "
@@ -68,7 +69,7 @@ class System:
         self._state = np.zeros(dim_state)
         self.action = np.zeros(dim_input)
         self._dim_full_state = dim_state + (dim_disturb if is_disturb else 0)  # systems.py:136-145
-        if is_disturb and self._sys_id != N.SYS_2TANK:  # systems.py:303-306, 365-368
+        if is_disturb and self._sys_id != N.SYS_2TANK:  # systems.py:303-306, 365-368 (a hip_policy with `disturb`: the same filter)
             self.sigma_disturb, self.mu_disturb, self.tau_disturb = pars_disturb[0], pars_disturb[1], pars_disturb[2]
         self.dtype, self.device, self.seed = dtype, device, int(seed)
         self._ops = None  # lazily created operator engine (batch 1: rcg_rhs takes any number of points)

@@ -16,9 +16,12 @@ Sys2Tank at the same shape.
 T ticks per launch (policies with TICKS): the first-use compile time of a k_ticks and of a k_ticks_mem program,
 and the rate of rcg_control_ticks(T = 512) against 512 single ticks on the same handle at B = 1024, K = 64, Nactor = 10, f32 and
 f64, interleaved, for the pendulum, the pendulum with the output map and a Sys2Tank copy next to the built-in Sys2Tank.
+The disturbance model (policies with DD / disturb): the first-use compile time of the disturb program
+(k_sim_dist, k_rhs_full) and, from the dispatches' own stamps, the disturbed env step (k_sim_dist) of the pendulum at 65 536
+envs next to the undisturbed k_sim of a handle of the same shape, f32 and f64, interleaved.
 GPU box only; no torch.
 
-    python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks]      (search, ticks: that section alone)
+    python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks | disturb]      (search, ticks, disturb: that section alone)
 """
 import os
 import sys
@@ -212,8 +215,60 @@ def ticks_rows(Bt=1024, Kt=64, T=512):
             e.close()
 
 
+# ---- the disturbance model on policies with DD / disturb ------------------------------------------------------
+DISTURB_MEMBER = r'''
+  template <typename real>
+  __device__ __forceinline__ static void disturb(const Pre<real>& q, const real* x, const real*, const real* w, real* d) {
+    d[1] = fma_r(q.inv_ml2 * cos(x[0]), w[0], d[1]);
+  }
+};
+'''
+
+
+def disturb_rows(Bd=65536, n_sub=1, reps=50):
+    src = PENDULUM.replace("PendulumT", "PendulumDisturbProbe").replace(
+        "static constexpr int DS = 2, DU = 1, NP = 3;", "static constexpr int DS = 2, DU = 1, NP = 3;\n  static constexpr int DD = 1;")
+    pend = N.register_system("PendulumDisturbProbe", src.replace("\n};\n", DISTURB_MEMBER), 2, 1, 3)
+    assert pend["dd"] == 1
+    rng = np.random.default_rng(3)
+    for dtype in ("f32", "f64"):
+        engines = []
+        for tag, dist in (("k_sim_dist (disturbed)", True), ("k_sim (undisturbed)", False)):
+            kw = dict(is_disturb=True, pars_disturb=[[2.0], [0.5], [1.5]], seed=1) if dist else {}
+            e = Engine(EngineConfig(sys_id=pend["sys_id"], batch=Bd, dtype=dtype, Nactor=NH, pars=[1.3, 9.81, 0.7],
+                                    ctrl_bnds=np.array([[-5.0, 5.0]]), R1=np.diag([10.0, 1.0, 0.1]), dt_sim=0.01, sampling_time=0.01,
+                                    pred_step_size=0.02, **kw))
+            e.set_state(rng.uniform(-1, 1, (Bd, 2)))
+            e.set_field(N.FIELD_ACTION, rng.uniform(-5, 5, (Bd, 1)))
+            t0 = time.perf_counter()
+            e.sim_step(n_sub)
+            e.synchronize()
+            first = time.perf_counter() - t0
+            for _ in range(5):
+                e.sim_step(n_sub)
+            e.synchronize()
+            e.profile([N.KERNEL_SIM])
+            engines.append((tag, e, first))
+        for _ in range(5):  # interleaved: ten env steps of each handle in turn
+            for tag, e, first in engines:
+                for _ in range(reps // 5):
+                    e.sim_step(n_sub)
+                e.synchronize()
+        for tag, e, first in engines:
+            t = e.profile_samples(N.KERNEL_SIM) * 1e-3
+            blocks = np.median(t.reshape(5, -1), axis=1) * 1e6
+            ll = e.last_launch(N.KERNEL_SIM)
+            print(f"disturb {dtype} {tag:24s} {ll['kernel']}: first rcg_sim_step {first:.2f} s "
+                  f"({'compiles the disturb program' if 'dist' in ll['kernel'] else 'nothing to compile'}); {n_sub} substep(s) at {Bd} envs: "
+                  f"{np.median(t) * 1e6:.2f} us (medians of the five blocks {blocks.min():.2f} .. {blocks.max():.2f})")
+            e.close()
+
+
 if ONLY == "search":
     search_rows()
+    sys.exit(0)
+if ONLY == "disturb":
+    disturb_rows()
     sys.exit(0)
 if ONLY == "ticks":
     ticks_rows()
@@ -336,3 +391,4 @@ for name, e, cand in engines:
 
 search_rows()
 ticks_rows()
+disturb_rows()
