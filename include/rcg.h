@@ -84,7 +84,11 @@ typedef enum rcg_where { RCG_HOST = 0, RCG_DEVICE = 1 } rcg_where;
 
 /* rcg_cfg.flags */
 #define RCG_FLAG_HAS_TARGET 0x1          /* observation_target != [] (controllers.py:1069)              */
-#define RCG_FLAG_PER_ENV_PARS 0x2        /* pars is a [np][B] device tensor (RCG_FIELD_PARS), not cfg.pars */
+#define RCG_FLAG_PER_ENV_PARS 0x2        /* pars is a [np][B] device tensor (RCG_FIELD_PARS), not cfg.pars; a system
+                                            without parameters (np = 0: Sys3WRobotNI, a registered policy with NP = 0)
+                                            accepts the flag and ignores it: RCG_FIELD_PARS is not allocated
+                                            (rcg_field_bytes 0, rcg_set_field / rcg_get_field RCG_ERR_BAD_ARG) and
+                                            every result is that of a handle without the flag */
 #define RCG_FLAG_REF_LAG 0x4             /* rollout starts from the state before the last substep
                                             (reference loop order, presets/main_3wrobot.py:425-428)    */
 #define RCG_FLAG_ACCUM_EVERY_SUBSTEP 0x8 /* upd_accum_obj every sim step (controllers.py:1093 quirk)    */
