@@ -103,7 +103,14 @@ typedef enum rcg_field {
   RCG_FIELD_ACCUM = 2,       /* [B]      real    CtrlOptPred.accum_obj_val                        */
   RCG_FIELD_STEP_IDX = 3,    /* [B]      int32   control ticks done in the current episode        */
   RCG_FIELD_EPISODE_IDX = 4, /* [B]      int32                                                    */
-  RCG_FIELD_STATUS = 5,      /* [B]      uint32  bit0: non-finite state seen, env frozen          */
+  RCG_FIELD_STATUS = 5,      /* [B]      uint32  bit0: non-finite state seen, env frozen.  An env whose state turns
+                                non-finite inside a simulation step is FROZEN: STATE and STATE_PREV keep their last finite values
+                                (the values the step started from; an env that enters a step with a NaN keeps that), the bit is
+                                set and no entry point steps the env again - one rule in every kernel that steps an env, the same
+                                result whether the bit was set by this tick's step or stood before it.  A tick still decides for,
+                                counts, charges and (RQL / SQL) pushes and fits a frozen env (rcg_control_tick); its neighbours in
+                                a wave are not affected by a bit.  rcg_episode_reset clears the flag; a caller may set or clear
+                                it (rcg_set_field).  tests/test_hip_freeze_paths.py pins all of this on every tick path.           */
   RCG_FIELD_PARS = 6,        /* [np][B]  real    only with RCG_FLAG_PER_ENV_PARS                  */
   RCG_FIELD_STATE_INIT = 7,  /* [ds][B]  real    Simulator.state_full_init                        */
   RCG_FIELD_STATE_PREV = 8,  /* [ds][B]  real    state before the last RK4 substep                */
@@ -403,7 +410,18 @@ int rcg_actor_argmin(rcg_handle* h, const void* cand, int32_t K, const void* obs
 /* One env.control-step for every env (the loop body of presets/main_3wrobot.py:419-429):
  * sim_step x substeps_per_tick -> [RQL/SQL: buffer push + critic fit] -> actor argmin over K
  * candidates -> ACTION := winner's first action -> ACCUM += stage_obj(obs, action)*sampling_time ->
- * STEP_IDX += 1.  cand as rcg_actor_argmin. */
+ * STEP_IDX += 1.  cand as rcg_actor_argmin.
+ * A frozen env (RCG_FIELD_STATUS bit 0, set before the tick or by its env step) goes through everything but the step:
+ *   not stepped   STATE and STATE_PREV stay as they are;
+ *   decided for   from its frozen state, as rcg_actor_argmin on that state decides: BEST_J, BEST_IDX and ACTION are written (a state
+ *                 that makes every candidate's cost non-finite: index 0 and +inf);
+ *   counted       STEP_IDX += 1;
+ *   charged       ACCUM += stage_obj(out(STATE), ACTION) * sampling_time (+inf or NaN where the frozen state makes it so);
+ *   pushed        RQL / SQL: (out(STATE), the held ACTION) enters the buffers every tick and the fit runs on them (non-finite rows
+ *                 leave the weights at the fit's start point, as rcg_critic_update does).
+ * The same holds for rcg_control_ticks, rcg_control_tick_n, a tick in two halves, rcg_control_tick_opt / _search / _nominal (the
+ * optimiser and the search keep a frozen env's ACTION finite and inside ctrl_bnds) and rcg_loop_step.  rcg_episode_reset clears
+ * the flag. */
 int rcg_control_tick(rcg_handle* h, const void* cand, int32_t K);
 /* T consecutive rcg_control_tick(h, NULL, K) - the loop of presets/main_3wrobot.py:415-468 for T sampling periods with
  * the generated candidate grid - in ONE kernel launch: each env's wave keeps state, held action, ACCUM and STEP_IDX (and,
@@ -538,7 +556,8 @@ int rcg_critic_update(rcg_handle* h, int32_t do_fit);
 int rcg_critic_fit(rcg_handle* h);
 /* Episode boundary (Simulator.reset, simulator.py:197-204; CtrlOptPred.reset, controllers.py:1046):
  * RETURNS := ACCUM; ACCUM := 0; STATE := STATE_INIT; ACTION := action_init; STEP_IDX := 0;
- * EPISODE_IDX += 1.  Critic weights and buffers are retained, as in the reference. */
+ * EPISODE_IDX += 1; STATUS := 0 (a frozen env starts the next episode from STATE_INIT like every other).  Critic weights and
+ * buffers are retained, as in the reference. */
 int rcg_episode_reset(rcg_handle* h);
 /* Summary of `RETURNS` (from_accum == 0) or of the running ACCUM (from_accum != 0) over this
  * handle's envs; returns_out (host, [B] real, may be NULL) receives the per-env values. */
