@@ -29,7 +29,8 @@ extern "C" {
 
 #define RCG_VERSION 125 /* 124 + rcg_system_has_ticks (T ticks per launch for a registered policy with TICKS = true).
                            rcg_system_disturb_dim (the disturbance model of a registered policy with DD / disturb) was added
-                           WITHOUT a version bump: a caller detects the feature by the symbol itself */
+                           WITHOUT a version bump: a caller detects the feature by the symbol itself.  So was
+                           rcg_system_has_loop (rcg_loop_step for a registered policy with LOOP = true) */
 
 /* ---- limits ------------------------------------------------------------------------------- */
 #define RCG_MAX_DS 5    /* largest dim_state of the built-in systems            */
@@ -206,9 +207,9 @@ int rcg_device_count(void);
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
  * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  The nominal
- * controllers and rcg_loop_step - and, without SEARCH (below), rcg_actor_search and rcg_control_tick_search, without TICKS
- * (below) rcg_control_ticks, without the disturbance model (below) rcg_create with RCG_FLAG_DISTURB - return
- * RCG_ERR_UNSUPPORTED with the handle untouched.
+ * controllers - and, without SEARCH (below), rcg_actor_search and rcg_control_tick_search, without TICKS (below)
+ * rcg_control_ticks, without LOOP (below) rcg_loop_step, without the disturbance model (below) rcg_create with
+ * RCG_FLAG_DISTURB - return RCG_ERR_UNSUPPORTED with the handle untouched.
  * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
  * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
  * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
@@ -231,6 +232,15 @@ int rcg_device_count(void);
  * before the call enqueues anything (a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error and the handle
  * untouched); the opt-in adds nothing to the registration itself.  Without TICKS rcg_control_ticks is RCG_ERR_UNSUPPORTED and
  * rcg_control_tick_n loops single ticks.
+ * The fused loop step: a policy opts in with `static constexpr bool LOOP = true;` (optional, default false).  rcg_loop_step and
+ * its two halves then run on k_loop and - the plain MPC sample - on the LOOP instance of k_actor_opt, the kernels the built-in
+ * systems run, with the same launches (rcg_last_launch).  With an output map the stage cost and the decision observe
+ * y = out(STATE) and the row ends with it (rcg_loop_step).  The loop program of a handle (element type, target setting: k_loop
+ * and, when the policy has jac_T - and out_jac_T with out -, that one k_actor_opt instance) is compiled the first time the
+ * handle calls rcg_loop_step(_begin), before the call enqueues anything (a compile error is RCG_ERR_BAD_ARG with hipRTC's log in
+ * rcg_last_error and the handle untouched); the opt-in adds nothing to the registration itself.  RCG_LOOP_DECIDE needs jac_T
+ * (out_jac_T with out): without, it is RCG_ERR_UNSUPPORTED naming the member, and steps without it are served.  RQL / SQL
+ * need CRITIC as well.  Without LOOP rcg_loop_step(_begin) is RCG_ERR_UNSUPPORTED before any handle state is touched.
  * The disturbance model (System(is_disturb=1), systems.py:140-145): a policy opts in with the two members
  *   static constexpr int DD = 1;   // dim_disturb: 1 or 2 (RCG_ERR_UNSUPPORTED otherwise)
  *   template <typename real>
@@ -269,9 +279,13 @@ int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks);
  * systems, DD for a registered policy with the `disturb` member, 0 for one without (rcg_create refuses RCG_FLAG_DISTURB for
  * it).  RCG_ERR_BAD_ARG for an id that names no system and for dd == NULL.  (Added without a version bump, RCG_VERSION.) */
 int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd);
+/* whether a system runs the fused loop step (rcg_loop_step, _begin / _end): 1 for the built-in ones and for a registered policy
+ * with LOOP = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system and for yes == NULL.  (Added without a version
+ * bump, RCG_VERSION: the symbol itself is how a caller detects that registered systems are served.) */
+int rcg_system_has_loop(int32_t sys_id, int32_t* yes);
 /* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
  * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs,
- * k_actor_search instances, k_ticks / k_ticks_mem instances, disturb programs).  Writes at
+ * k_actor_search instances, k_ticks / k_ticks_mem instances, disturb programs, loop programs).  Writes at
  * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
 int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 
@@ -365,12 +379,16 @@ int rcg_sim_step_h(rcg_handle* h, int32_t n_substeps, double step);
  *                               RCG_LOOP_DECIDE: rcg_actor_optimize, `iters` iterations from action_sqn_init, the rollout from
  *                               STATE_PREV - the loop hands the controller System._state one iteration late (controllers.py:
  *                               1056-1061) - with STATE as the observation; ACTION := the optimum's first action, ACTION_SQN := it
- *   CtrlOptPred.stage_obj       rho(STATE, ACTION)
- * out (host): [B][ds + du + 2 (+ dc in RQL / SQL)] doubles per env: state, action, stage_obj, best_J (NaN without
- * RCG_LOOP_DECIDE), W_CRITIC.  ACCUM / STEP_IDX are not touched (upd_accum_obj is the caller's multiply-add; the caller decides
+ *   CtrlOptPred.stage_obj       rho(STATE, ACTION); a system with an output map: rho(y, ACTION), y = out(STATE) as rcg_out forms
+ *                               it, which is also what the decision observes and the push stores
+ * out (host): [B][ds + du + 2 (+ dc in RQL / SQL) (+ dy with an output map)] doubles per env: state, action, stage_obj, best_J
+ * (NaN without RCG_LOOP_DECIDE), W_CRITIC, and - a registered system whose policy defines out - the observation y.  ACCUM / STEP_IDX are not touched (upd_accum_obj is the caller's multiply-add; the caller decides
  * from its clock which steps are samples).  Every number equals what the separate calls (rcg_set_field, rcg_sim_step_h,
  * rcg_critic_update, rcg_actor_optimize, rcg_stage_obj) leave, bit for bit.  Handles whose rows fit the 16-KB pinned buffer
- * (3-wheel robot, MPC: up to 200 envs); no disturbance model.  Launches: ONE for a step that is no sample (k_loop), ONE for a
+ * (a row, the action handed in and one sequence number per env: 3-wheel robot, MPC: 12 doubles, up to 170 envs); no
+ * disturbance model.  Served: the built-in systems, and a registered system whose policy opts in with LOOP = true
+ * (rcg_register_system, rcg_system_has_loop; RCG_LOOP_DECIDE needs its jac_T, and out_jac_T with out) - any other is
+ * RCG_ERR_UNSUPPORTED naming the member, before anything is enqueued or any handle state is touched.  Launches: ONE for a step that is no sample (k_loop), ONE for a
  * sample with the plain MPC decision (diagonal stage cost, no curvature pairs - every MPC preset: k_actor_opt does the
  * iteration's head and tail itself, rcg_last_launch variant bit 3), three otherwise. */
 #define RCG_LOOP_DECIDE 1

@@ -74,6 +74,10 @@ class CtrlOptPred:
         info = type(sys_obj)._hip_info if type(sys_obj).hip_policy is not None else None
         self._runtime_sys = info is not None
         self._has_out = bool(info is not None and info.get("has_out"))
+        # the fused loop step (rcg_loop_step) serves a compiled system whose policy opts in with `static constexpr bool LOOP = true;`
+        # and has what the fused decision - the on-device optimiser - needs
+        self._rt_fuse = info is None or bool(info.get("has_loop") and info["has_jac"]
+                                             and (not info.get("has_out") or info.get("has_out_jac")))
         if info is not None:
             if mode != "MPC" and not info.get("has_critic"):
                 raise NotImplementedError(f"{type(sys_obj).__name__} is compiled from hip_policy: mode {mode!r} needs the critic "
@@ -167,6 +171,7 @@ class CtrlOptPred:
         # the fused loop step (rcg_loop_step, Simulator.sim_step): what it computed ahead for compute_action / stage_obj
         self._dtype = dtype
         self._fz = None
+        self._fused_obs = None    # the observation [B, dy] the last fused step computed (a system with an output map)
         self._fused_dirty = True  # the handle's STATE / buffers / weights must be uploaded before the next fused step
         self.fused_steps = 0      # statistics: loop iterations served by one native call ...
         self.fused_decisions = 0  # ... and decisions of compute_action taken from them
@@ -200,15 +205,21 @@ class CtrlOptPred:
     # ------------------------------------------------------------------ fused loop step
     def _can_fuse(self, sim):
         """One native call per loop iteration (rcg_loop_step) when: the decision is the on-device optimiser, no disturbance
-        model, same batch and element type as the simulator, rows that fit the handle's pinned buffer, a non-empty TD stack."""
-        key = (self.candidates is None, self._use_gradient)
+        model, same batch and element type as the simulator, rows that fit the handle's pinned buffer, a non-empty TD stack.
+        A system compiled from hip_policy: its policy has LOOP and jac_T (out_jac_T with out), and the simulator takes one
+        substep per step - the device rolls a fused decision out from the state before the LAST substep, compute_action
+        accepts it against the state before the whole step, and the two are the same state for one substep only."""
+        key = (self.candidates is None, self._use_gradient, sim.n_substeps)
         hit = getattr(self, "_can_fuse_cache", None)
         if hit is not None and hit[0]() is sim and hit[1] == key:  # (a weak reference: an id() may be reused by a later object)
             return hit[2]
-        row = self.dim_output + self.dim_input + 2 + (self.dim_critic if self.mode != "MPC" else 0)
-        ok = (not self._runtime_sys and sim.sys is self.sys and sim.B == self.B and sim.dtype == self._dtype and not sim.is_disturb
+        # rcg_loop_step's own bound: a row, the action handed in and the sequence number of every env in the pinned buffer
+        row = self._eng_raw._loop_dims[0]
+        ok = (self._rt_fuse and sim.sys is self.sys and sim.B == self.B and sim.dtype == self._dtype and not sim.is_disturb
               and self.candidates is None and self._use_gradient and (self.mode == "MPC" or self.Ncritic - 1 >= 1)
-              and self.B * (row + self.dim_input) * 8 <= 16384)
+              and self.B * (row + self.dim_input + 1) * 8 <= 16384
+              and (not self._runtime_sys or sim.n_substeps == 1)
+              and (not self._has_out or self.sys.dtype == self._dtype))  # (the row's y stands for System.out's)
         import weakref
 
         self._can_fuse_cache = (weakref.ref(sim), key, ok)
@@ -285,7 +296,7 @@ class CtrlOptPred:
                     and spec[1] == actb
                     and not (push and not self._same(self._b(self.action_curr, self.dim_input), act))):
                 self._spec = None
-                res = self._eng_raw.loop_step_end()
+                res = self._eng_raw.loop_step_end(with_obs=self._has_out)
                 self.spec_hits += 1
             else:
                 self._spec_drop()
@@ -295,9 +306,13 @@ class CtrlOptPred:
                 return None
             if self._fused_dirty:
                 self._fused_sync(np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self._eng_raw.ds])
-            res = self._eng_raw.loop_step(act, step, sim.n_substeps, decide=tick, push=push, fit=fit, iters=self.opt_iters)
-        st, a, stage, bj, w = res
-        stb = st.tobytes()
+            res = self._eng_raw.loop_step(act, step, sim.n_substeps, decide=tick, push=push, fit=fit, iters=self.opt_iters,
+                                          with_obs=self._has_out)
+        st, a, stage, bj, w = res[:5]
+        # the observation of the new state: the state, or - an output map - the row's y = out(state), which Simulator.sim_step
+        # takes for its `observation` (no rcg_out call on this path)
+        self._fused_obs = res[5] if self._has_out else None
+        stb = st.tobytes() if self._fused_obs is None else self._fused_obs.tobytes()
         if tick:  # what compute_action must be asked with for the decision to be the one it would make: the new state as the
             # observation, the state before the step (the simulator still holds it) as state_sys
             xsb = np.asarray(sim.state_full, dtype=float).reshape(self.B, -1)[:, :self._eng_raw.ds].tobytes()

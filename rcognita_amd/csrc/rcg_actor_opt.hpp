@@ -227,11 +227,12 @@ __device__ __forceinline__ void critic_grad_with(const real* chi, const real* y,
 // System.receive_action + Simulator.sim_step, the fields written as k_loop writes them - and decides from (obs = the new STATE,
 // state_sys = STATE_PREV) held in its registers; after the decision it does k_loop's tail (stage_obj of the new state and the
 // decided action, the row and the sequence number into the pinned host buffer).  Same device functions as the three launches.
+// With an output map (a registered policy with LOOP) the stepped state (DS registers) and its observation y_0 = out(state) (DY
+// registers) are kept apart: the decision observes y_0, the tail writes both.
 template <typename Sys, typename real, bool TGT, bool GENERIC, bool PAIRS, bool LOOP = false>
 __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const KParams<real> P) {
   constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, NP = Sys::NP, NPS = NP > 0 ? NP : 1, G = OPT_G;
   constexpr bool OUT = HasOut<Sys>::value;
-  static_assert(!(OUT && LOOP), "rcg_loop_step serves the built-in systems only");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int lane = threadIdx.x & 63;
   const int wave_in_wg = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -259,7 +260,16 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
   const bool mine = lane < ng;       // lane == env view
   const long be = b0 + (mine ? lane : 0);
   real y0e[DY], xse[DS], pve[NPS], w[DU], w2[DU], on[sys_dxy<Sys>()];
-  if constexpr (LOOP) {
+  [[maybe_unused]] real xne[(LOOP && OUT) ? DS : 1];  // LOOP with an output map: the stepped state, apart from the observation y0e
+  if constexpr (LOOP && OUT) {
+    real ul[DU];
+    if (mine) {
+      loop_head<Sys, real>(A.loop, P, be, ul, xne, xse);
+    } else {
+#pragma unroll
+      for (int c = 0; c < DS; ++c) xne[c] = xse[c] = (real)0;  // an idle lane stands for no env (its values are never used)
+    }
+  } else if constexpr (LOOP) {
     real ul[DU];
     if (mine) {
       loop_head<Sys, real>(A.loop, P, be, ul, y0e, xse);
@@ -283,7 +293,10 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
 #pragma unroll
   for (int i = 0; i < NP; ++i) pve[i] = A.pars_env ? A.pars_env[(long)i * B + be] : P.pars[i];
   const auto pre_e = Sys::template prepare<real>(pve);
-  if constexpr (OUT) obs_of_raw<Sys, real>(pre_e, A.obs_x, on, y0e);
+  if constexpr (LOOP && OUT)
+    loop_obs<Sys, real>(pre_e, xne, y0e);  // y_0 = out(the stepped state), as obs_of_raw forms it from a handed-in STATE
+  else if constexpr (OUT)
+    obs_of_raw<Sys, real>(pre_e, A.obs_x, on, y0e);
 #pragma unroll
   for (int c = 0; c < DU; ++c) {
     w[c] = P.hi[c] - P.lo[c];
@@ -724,7 +737,10 @@ __global__ __launch_bounds__(256) void k_actor_opt(const OptArgs<real> A, const 
     if (A.n_iter) A.n_iter[be] = used;
     if (A.accum) A.accum[be] = accum_update<Sys, TGT, real>(P, y0e, a, A.accum[be]);
     if (A.step_idx) A.step_idx[be] += 1;
-    if constexpr (LOOP) loop_tail<Sys, real>(A.loop, P, be, a, y0e, (double)Jinc);
+    if constexpr (LOOP && OUT)
+      loop_tail_out<Sys, real>(A.loop, P, be, a, xne, y0e, (double)Jinc);
+    else if constexpr (LOOP)
+      loop_tail<Sys, real>(A.loop, P, be, a, y0e, (double)Jinc);
   }
 }
 

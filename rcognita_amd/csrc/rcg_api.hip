@@ -103,7 +103,7 @@ static bool system_dims(int sys_id, RtcDims* d, const RtcSystem** rtc = nullptr)
     d->ds = d->dy = kDims[sys_id][0];
     d->du = kDims[sys_id][1];
     d->np = kDims[sys_id][2];
-    d->has_jac = d->has_critic = d->has_search = d->has_ticks = true;
+    d->has_jac = d->has_critic = d->has_search = d->has_ticks = d->has_loop = true;
     d->dd = sys_id == RCG_SYS_2TANK ? 1 : 2;  // dim_disturb of the presets (main_*.py dim_disturb)
     return true;
   }
@@ -231,6 +231,14 @@ int rcg_system_has_ticks(int32_t sys_id, int32_t* has_ticks) {
   RtcDims d;
   if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_ticks: bad sys_id %d", sys_id);
   if (has_ticks) *has_ticks = d.has_ticks ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_loop(int32_t sys_id, int32_t* yes) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_loop: bad sys_id %d", sys_id);
+  if (!yes) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_loop: null argument");
+  *yes = d.has_loop ? 1 : 0;
   return RCG_OK;
 }
 
@@ -1056,15 +1064,23 @@ int rcg_loop_step_begin(rcg_handle* h, const double* action_in, double step_h, i
   const bool critic = h->cfg.mode != RCG_MODE_MPC;
   const bool decide = flags & RCG_LOOP_DECIDE, push = critic && (flags & RCG_LOOP_PUSH), fit = push && (flags & RCG_LOOP_FIT);
   if (h->cfg.flags & RCG_FLAG_DISTURB) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: no disturbance model on this path");
-  if (h->rtc) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: not available for a system registered at run time");
+  if (h->rtc) {  // a registered system: its policy opts in with LOOP; a decision needs the optimiser's members
+    const int rc = rtc_loop_refusals(h, decide);
+    if (rc) return rc;
+  }
   if (fit && h->cfg.n_critic - 1 < 1) return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: an empty TD stack (Ncritic = 1) takes the separate calls");
-  const int B = h->cfg.batch, ds = h->ds, du = h->du, dc = critic ? h->dc : 0, row = ds + du + 2 + dc;
+  // a system with an output map: the row carries the observation y = out(state) behind the weights
+  const int B = h->cfg.batch, ds = h->ds, du = h->du, dc = critic ? h->dc : 0, row = ds + du + 2 + dc + (h->rtc_has_out ? h->dy : 0);
   const size_t out_bytes = (size_t)B * row * sizeof(double), in_bytes = (size_t)B * du * sizeof(double);
   if (out_bytes + in_bytes + (size_t)B * sizeof(double) > kBounceBytes)
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: %d envs do not fit the handle's %zu-byte pinned buffer (a small-batch entry point)",
                     B, kBounceBytes);
   if (decide) {
     const int rc = check_optimizer(h, "rcg_loop_step");
+    if (rc) return rc;
+  }
+  if (h->rtc) {  // the loop program, compiled on first use: a compile error leaves the handle untouched
+    const int rc = rtc_prepare_loop(h, push);
     if (rc) return rc;
   }
   if (!h->loop_pin) {

@@ -279,6 +279,7 @@ struct RtcDims {  // (`RtcDims d;` is the description of nothing)
   bool has_search = false;   // the policy opts in to the device search (static constexpr bool SEARCH = true): k_actor_search
   bool has_ticks = false;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
   int dd = 0;                // dim_disturb: the policy's DD when it has the `disturb` member (RCG_FLAG_DISTURB handles), else 0
+  bool has_loop = false;     // the policy opts in to the fused loop step (static constexpr bool LOOP = true): rcg_loop_step
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])
@@ -289,6 +290,12 @@ int rtc_prepare_tick(rcg_handle* h, const void* cand, int32_t K);
 int rtc_prepare_tick_opt(rcg_handle* h);  // ... and rcg_control_tick_opt
 // ... and rcg_control_tick_search (every mode): refuses a policy without SEARCH, else resolves the tick's search instance
 int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t warm);
+// rcg_loop_step(_begin) on a registered system.  rtc_loop_refusals: a policy without LOOP, or a decision asked of a policy
+// without jac_T (out_jac_T with out) - RCG_ERR_UNSUPPORTED naming the member, no handle state touched.  rtc_prepare_loop: the loop
+// program of the handle (and, for a critic push, the critic program's fit kernel) resolved - compiled on first use - before the
+// step enqueues anything
+int rtc_loop_refusals(rcg_handle* h, bool decide);
+int rtc_prepare_loop(rcg_handle* h, bool push);
 extern const SysVTable kVtRtc;
 // sets the thread's error text (rcg_last_error(NULL)) without rcg_fail's length limit: hipRTC's log
 void rcg_set_thread_error(const std::string& text);

@@ -6,7 +6,7 @@
 // instances through hipModuleLaunchKernel:
 //   at registration  a small probe program (the policy's optional members), then the f32 and f64 core programs: k_rhs,
 //                    k_stage_obj, k_sim, k_actor (streamed / generated x generic / diagonal stage cost x target, and the DIRECT
-//                    long-row form), k_actor_opt without LOOP when the policy has jac_T (and out_jac_T if it has out), k_out
+//                    long-row form), k_actor_opt without its LOOP form when the policy has jac_T (and out_jac_T if it has out), k_out
 //                    when the policy has an output map `out` (DY = dim_output; every kernel then observes y = out(x));
 //   on first use     one small program per instance, through one routine (lazy_function) and one cache (RtcSystem::lazy) keyed
 //                    by the name expression that selects the instance:
@@ -23,14 +23,17 @@
 //                    for rcg_rhs_full: k_sim_dist (with and without a target) and k_rhs_full (<name>_disturb.hip).  The adapter
 //                    generates Disturb<RcgRtcSys> from the two members in every unit that includes rcg_disturb.hpp, so the
 //                    k_ticks instances of such a policy run the disturbed env step too (TicksArgs::dist);
+//                    for a policy that opts in with `static constexpr bool LOOP = true`, the loop program of a handle's element
+//                    type and target setting, the first time the handle calls rcg_loop_step(_begin): k_loop and, when the policy
+//                    has jac_T (and out_jac_T with out), the LOOP instance of k_actor_opt (<name>_loop.hip);
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan / ticks_plan /
 // ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is
 // not compiled is refused with RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC
 // (rcg_create refuses RQL / SQL for it), the device search of a policy without SEARCH, T ticks per launch of a policy without
-// TICKS, the nominal controllers and rcg_loop_step; rcg_create refuses the disturbance model for a policy without `disturb`, and
-// under it RQL / SQL through k_ticks_mem, the two-halves tick and the fused env step stay refused or unfused as for the built-in
-// systems.  One mutex
+// TICKS, rcg_loop_step of a policy without LOOP (and its decision without jac_T), the nominal controllers; rcg_create refuses
+// the disturbance model for a policy without `disturb`, and under it RQL / SQL through k_ticks_mem, the two-halves tick and the
+// fused env step stay refused or unfused as for the built-in systems.  One mutex
 // guards the registry and every cache, the compiler runs outside it, and a handle keeps the functions it has resolved; nothing
 // is ever unregistered or unloaded (handles point into the registry).
 #include <hip/hiprtc.h>
@@ -94,7 +97,7 @@ bool is_identifier(const char* s) {
 // The generated unit: the kernel headers of its flavour (Core: the probe, the core programs and the k_actor_dma instances), the
 // policy (its own file name and line numbers in hipRTC's log), the adapter that supplies the optional members and the checks of
 // the declared dimensions.
-enum class Unit { Core, Critic, Search, Ticks, Disturb };
+enum class Unit { Core, Critic, Search, Ticks, Disturb, Loop };  // (Loop: the Core unit's headers hold k_loop and k_actor_opt)
 std::string unit_source(const RtcSystem& S, Unit unit) {
   const bool critic = unit == Unit::Critic, search = unit == Unit::Search, ticks = unit == Unit::Ticks;
   const bool disturb = unit == Unit::Disturb;
@@ -146,8 +149,10 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "template <class S, class = void> struct dist { static constexpr bool v = false; };\n"
          "template <class S> struct dist<S, void_t<decltype(&S::template disturb<float>)>> { static constexpr bool v = true; };\n"
          "template <class S> struct ddv { static constexpr int v = dist<S>::v ? (dd<S>::v == 0 ? -1 : dd<S>::v) : 0; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD> __global__ "
-         "void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct lp { static constexpr bool v = false; };\n"
+         "template <class S> struct lp<S, void_t<decltype(S::LOOP)>> { static constexpr bool v = S::LOOP; };\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD, bool LP> "
+         "__global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + " {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
@@ -265,6 +270,15 @@ template <typename real>
 std::string expr_opt(bool tgt, bool gen, bool pairs) {
   return std::string("rcg::k_actor_opt<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ", " + tf(gen) + ", " + tf(pairs) +
          ">";
+}
+// the loop program (rcg_loop_step): the glue kernel, and the LOOP instance of the plain MPC decision (op_optimize's)
+template <typename real>
+std::string expr_loop() {
+  return std::string("rcg::k_loop<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+template <typename real>
+std::string expr_opt_loop(bool tgt) {
+  return std::string("rcg::k_actor_opt<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ", false, false, true>";
 }
 // k_actor_dma's TGT parameter is the system's own for the preset-cost variants, true for DMA_MPC_GEND / GENF (rcg_dma_launch.hpp);
 // zw != 0: the zero-weight instance of DMA_MPC_G1 (rcg_actor_dma.hpp::dma_zero_w) - a registered copy of a robot resolves to
@@ -452,7 +466,21 @@ int disturb_function(rcg_handle* h, int want, hipFunction_t* fn) {
   return lazy_function(h, Unit::Disturb, "disturb", exprs, want, fn);
 }
 
-// a member of the table that the policy did not opt in to with `member` (CRITIC, SEARCH, TICKS)
+// The loop program of a handle's (element type, target setting) for a policy with LOOP: k_loop and - when the policy has jac_T (and
+// out_jac_T with out) - the LOOP instance of k_actor_opt at that target setting, which is then the expression that keys the
+// program; `want`: which of the two
+enum { LOOP_GLUE = 0, LOOP_OPT = 1 };
+bool rtc_has_opt(const RtcDims& d) { return d.has_jac && (!d.has_out || d.has_out_jac); }
+template <typename real>
+int loop_function(rcg_handle* h, int want, hipFunction_t* fn) {
+  if (!h->rtc->dims.has_loop) return RCG_ERR_UNSUPPORTED;  // (the callers refuse by name first)
+  std::vector<std::string> exprs{expr_loop<real>()};
+  if (rtc_has_opt(h->rtc->dims)) exprs.push_back(expr_opt_loop<real>((h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0));
+  if ((size_t)want >= exprs.size()) return RCG_ERR_UNSUPPORTED;
+  return lazy_function(h, Unit::Loop, "loop", exprs, (size_t)want, fn);
+}
+
+// a member of the table that the policy did not opt in to with `member` (CRITIC, SEARCH, TICKS, LOOP)
 int refuse_opt_in(rcg_handle* h, const char* who, const char* member) {
   return rcg_fail(h, RCG_ERR_UNSUPPORTED,
                   "%s: not available for a system registered at run time whose policy does not opt in with %s (%s)", who, member,
@@ -630,7 +658,8 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
     return rcg_fail(h, RCG_ERR_UNSUPPORTED,
                     "rcg_actor_optimize: the policy %s defines out but no out_jac_T (the adjoint of its output map)",
                     h->rtc->name.c_str());
-  if (h->loop_io.on) return refuse(h, "rcg_loop_step");
+  const bool loop = h->loop_io.on;  // rcg_loop_step's one-launch sample (op_optimize): head and tail of the iteration in this launch
+  if (loop && !h->rtc->dims.has_loop) return refuse_opt_in(h, "rcg_loop_step", "LOOP");
   return by_dtype(h, [&](auto r) {
     using real = decltype(r);
     OptArgs<real> A;
@@ -639,7 +668,15 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
     if (rc) return rc;
     KParams<real> P = params<real>(h);
     hipFunction_t f;
-    rc = core_function<real>(h, expr_opt<real>(L.tgt, L.generic, L.pairs), &f);
+    if (loop) {  // the LOOP instance: plain MPC on the handle's own fields alone, as op_optimize asks
+      if (L.generic || L.pairs || obs || state_sys != h->f[RCG_FIELD_STATE_PREV] || u_init || tick)
+        return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: the one-launch sample is the plain MPC instance on the handle's own fields");
+      fill_loop_args<real>(h, A.loop, h->loop_io.act_in, h->loop_io.n_substeps, 1, 1, 1, h->loop_io.dc, h->loop_io.out,
+                           h->loop_io.flag, h->loop_io.seq);
+      rc = loop_function<real>(h, LOOP_OPT, &f);
+    } else {
+      rc = core_function<real>(h, expr_opt<real>(L.tgt, L.generic, L.pairs), &f);
+    }
     if (rc) return rc;
     if (tick && sim_first) {
       rc = sim_step<real>(h, h->cfg.substeps_per_tick);
@@ -650,7 +687,7 @@ int rtc_optimize(rcg_handle* h, int32_t iters, const void* obs, const void* stat
     ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
     void* args[] = {&A, &P};
     rc = launch(h, f, L.grid, L.block, L.lds, args);
-    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, L.variant, OPT_G);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_ACTOR_OPT, L.variant | (loop ? 8 : 0), OPT_G);
     return rc;
   });
 }
@@ -819,26 +856,39 @@ int rtc_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t round0, const v
     return rc;
   });
 }
-int rtc_loop(rcg_handle* h, const double*, int32_t, int32_t, int32_t, int32_t, int32_t, double*, double*, double) {
-  return refuse(h, "rcg_loop_step");
+// rcg_loop_step's glue kernel: op_loop's arguments (fill_loop_args) and grid on the loop program's k_loop
+int rtc_loop(rcg_handle* h, const double* act_in, int32_t n_substeps, int32_t do_sim, int32_t do_tail, int32_t decided, int32_t dc,
+             double* out, double* flag, double seq) {
+  if (!h->rtc->dims.has_loop) return refuse_opt_in(h, "rcg_loop_step", "LOOP");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = loop_function<real>(h, LOOP_GLUE, &f);
+    if (rc) return rc;
+    LoopArgs<real> A;
+    fill_loop_args<real>(h, A, act_in, n_substeps, do_sim, do_tail, decided, dc, out, flag, seq);
+    KParams<real> P = params<real>(h);
+    void* args[] = {&A, &P};
+    return launch(h, f, dim3(blocks_for(h->cfg.batch, 64)), dim3(64), 0, args);
+  });
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW, DD> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E;
-// DD: the policy's DD when it has `disturb`, else 0)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW, DD, LP> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E;
+// DD: the policy's DD when it has `disturb`, else 0; LP: the policy's LOOP)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
-                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v>";
+                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v, rcg::rtc::lp<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S, Unit::Core), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[10];
+  long v[11];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 10 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 11 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -849,7 +899,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 10) {
+  if (n != 11) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -863,6 +913,7 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.has_ticks = v[7] != 0;
   S.zw = (unsigned)v[8];
   S.dims.dd = (int)v[9];
+  S.dims.has_loop = v[10] != 0;
   return RCG_OK;
 }
 
@@ -945,6 +996,27 @@ int rtc_prepare_tick_opt(rcg_handle* h) {
                     h->rtc->name.c_str(), d.has_out ? " / out_jac_T" : "");
   hipFunction_t fit;
   return critic_fit_function(h, &fit);
+}
+
+int rtc_loop_refusals(rcg_handle* h, bool decide) {
+  const RtcDims& d = h->rtc->dims;
+  if (!d.has_loop) return refuse_opt_in(h, "rcg_loop_step", "LOOP");
+  if (decide && !d.has_jac)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_loop_step: RCG_LOOP_DECIDE needs jac_T in the policy %s (the optimiser's adjoint sweep)",
+                    h->rtc->name.c_str());
+  if (decide && d.has_out && !d.has_out_jac)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED,
+                    "rcg_loop_step: RCG_LOOP_DECIDE needs out_jac_T in the policy %s (it defines out: the adjoint of its output map)",
+                    h->rtc->name.c_str());
+  return RCG_OK;
+}
+
+int rtc_prepare_loop(rcg_handle* h, bool push) {
+  hipFunction_t f;
+  int rc = by_dtype(h, [&](auto r) { return loop_function<decltype(r)>(h, LOOP_GLUE, &f); });
+  if (rc || !push) return rc;
+  if (!h->rtc->dims.has_critic) return refuse_opt_in(h, "rcg_loop_step", "CRITIC");
+  return critic_fit_function(h, &f);
 }
 
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims) {

@@ -259,6 +259,11 @@ class Engine:
         self._h = h
         self._loop_fn = L.rcg_loop_step
         self._loop_begin_fn, self._loop_end_fn = L.rcg_loop_step_begin, L.rcg_loop_step_end
+        # doubles per env of a loop step's row (rcg_loop_step): with an output map it ends with the observation
+        has_out = C.c_int32(0)
+        N.check(L.rcg_system_output_info(int(cfg.sys_id), None, C.byref(has_out), None))
+        row = self.ds + self.du + 2 + (self.dc if cfg.mode != "MPC" else 0)
+        self._loop_dims = (row + (self.dy if has_out.value else 0), row, bool(has_out.value))
 
     # ------------------------------------------------------------------ life cycle
     def close(self):
@@ -606,15 +611,25 @@ class Engine:
         else:
             N.check(N.lib().rcg_sim_step_h(self._h, int(n_substeps), float(step)), self._h)
 
-    def loop_step(self, action, step, n_substeps=1, decide=False, push=False, fit=False, iters=10):
+    def _loop_rows(self, out, with_obs):
+        """The rows of a loop step as the tuple ``loop_step`` returns."""
+        ds, du = self.ds, self.du
+        full, row, has_out = self._loop_dims
+        res = (out[:, :ds], out[:, ds:ds + du], out[:, ds + du], out[:, ds + du + 1],
+               out[:, ds + du + 2:row] if row > ds + du + 2 else None)
+        if with_obs:  # (without an output map the observation is the state)
+            res += (out[:, row:full] if has_out else out[:, :ds],)
+        return res
+
+    def loop_step(self, action, step, n_substeps=1, decide=False, push=False, fit=False, iters=10, with_obs=False):
         """One iteration of the reference's loop body in one native call and one host wait (rcg_loop_step): hold ``action
         [B, du]`` (None: the handle's own) over one simulation step of length ``step``, then - as asked - push the critic
         buffers, refit the critic, decide with the on-device optimiser (rollout from the state before the step), and
         evaluate the stage cost of (new state, action).  Returns ``(state [B, ds], action [B, du], stage_obj [B], best_J [B]
-        (NaN without ``decide``), w_critic [B, dc] or None)`` as float64."""
-        ds, du = self.ds, self.du
-        row = ds + du + 2 + (self.dc if self.cfg.mode != "MPC" else 0)
-        out = np.empty((self.B, row), dtype=np.float64)  # (fresh per call: the caller keeps views of it)
+        (NaN without ``decide``), w_critic [B, dc] or None)`` as float64; ``with_obs``: a sixth element, the observation
+        ``[B, dy]`` of the new state (y = out(state) of a system with an output map, which the device computed; else the state)."""
+        du = self.du
+        out = np.empty((self.B, self._loop_dims[0]), dtype=np.float64)  # (fresh per call: the caller keeps views of it)
         pa = None
         if action is not None:
             a = np.asarray(action, dtype=np.float64)
@@ -625,8 +640,7 @@ class Engine:
         rc = self._loop_fn(self._h, pa, step, n_substeps, flags, iters, out.ctypes.data)
         if rc:
             N.check(rc, self._h)
-        return (out[:, :ds], out[:, ds:ds + du], out[:, ds + du], out[:, ds + du + 1],
-                out[:, ds + du + 2:] if row > ds + du + 2 else None)
+        return self._loop_rows(out, with_obs)
 
     def loop_step_begin(self, action, step, n_substeps=1, decide=False, push=False, fit=False, iters=10):
         """Enqueue one loop iteration and return (rcg_loop_step_begin): the device runs it while the host goes on;
@@ -642,21 +656,18 @@ class Engine:
         if rc:
             N.check(rc, self._h)
 
-    def loop_step_end(self, drop=False):
+    def loop_step_end(self, drop=False, with_obs=False):
         """Wait for the pending iteration (rcg_loop_step_end) and return its rows as ``loop_step`` does; ``drop``: wait only."""
         if drop:
             rc = self._loop_end_fn(self._h, None)
             if rc:
                 N.check(rc, self._h)
             return None
-        ds, du = self.ds, self.du
-        row = ds + du + 2 + (self.dc if self.cfg.mode != "MPC" else 0)
-        out = np.empty((self.B, row), dtype=np.float64)  # (fresh per call: the caller keeps views of it)
+        out = np.empty((self.B, self._loop_dims[0]), dtype=np.float64)  # (fresh per call: the caller keeps views of it)
         rc = self._loop_end_fn(self._h, out.ctypes.data)
         if rc:
             N.check(rc, self._h)
-        return (out[:, :ds], out[:, ds:ds + du], out[:, ds + du], out[:, ds + du + 1],
-                out[:, ds + du + 2:] if row > ds + du + 2 else None)
+        return self._loop_rows(out, with_obs)
 
     def actor_argmin(self, cand=None, K=None, obs=None, state_sys=None):
         """Returns ``(action [B, du], best_J [B], best_idx [B] int32)``."""

@@ -95,7 +95,8 @@ class Simulator:
                 self._eng_stale = True
                 self.state_full = self._shape(st)
                 self.state = self.state_full[..., 0:self.dim_state]
-                self.observation = self.sys_out(self.state)
+                y = ctrl._fused_obs  # an output map: y = out(state) came with the step's row
+                self.observation = self.sys_out(self.state) if y is None else self._shape(y)
                 # what System.closed_loop_rhs leaves behind: the clipped action (systems.py:241-243); the controller's own last
                 # decision - the optimiser's iterates live inside the box - needs no clip
                 if self.sys.action is not getattr(ctrl, "_inb_action", None) and self.sys.ctrl_bnds.any():

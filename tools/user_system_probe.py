@@ -19,9 +19,14 @@ f64, interleaved, for the pendulum, the pendulum with the output map and a Sys2T
 The disturbance model (policies with DD / disturb): the first-use compile time of the disturb program
 (k_sim_dist, k_rhs_full) and, from the dispatches' own stamps, the disturbed env step (k_sim_dist) of the pendulum at 65 536
 envs next to the undisturbed k_sim of a handle of the same shape, f32 and f64, interleaved.
+The fused loop step (policies with LOOP): the first-use compile time of the loop program, and the simulation
+steps per second of the B = 1 drop-in loop (tools/b1_profile.py's bracket) for the pendulum (MPC), the pendulum with the output
+map (MPC, RQL) and a Sys2Tank copy next to the built-in Sys2Tank - fused, with Simulator.fuse = False and, when the root of
+another checkout with a built library is given, on that checkout (the parent commit), interleaved, medians of five.
 GPU box only; no torch.
 
     python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks | disturb]      (search, ticks, disturb: that section alone)
+    python tools/user_system_probe.py 1 1 5 loop [root of another checkout]
 """
 import os
 import sys
@@ -30,6 +35,8 @@ import time
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if len(sys.argv) > 5 and sys.argv[4] == "loop-worker":  # a worker of the loop section serves the checkout it is given
+    ROOT = os.path.abspath(sys.argv[5])
 sys.path.insert(0, ROOT)
 from rcognita_amd import Engine, EngineConfig  # noqa: E402
 from rcognita_amd import _native as N  # noqa: E402
@@ -264,6 +271,133 @@ def disturb_rows(Bd=65536, n_sub=1, reps=50):
             e.close()
 
 
+# ---- the fused loop step on policies with LOOP ----------------------------------------------------------------
+LOOP_CASES = (("pendulum", "MPC"), ("pendulum with out", "MPC"), ("pendulum with out", "RQL"), ("Sys2Tank copy", "MPC"),
+              ("Sys2Tank (built-in)", "MPC"))
+
+
+def loop_objects(name, mode):
+    """System, controller and simulator of one case, wired as the presets wire them (simulation steps of dt / 2)."""
+    from rcognita_amd import controllers, simulator, systems
+
+    tank_src = open(os.path.join(ROOT, "rcognita_amd", "csrc", "rcg_systems.hpp")).read()
+    i = tank_src.index("struct Sys2Tank {")
+    tank_src = tank_src[i:tank_src.index("\n};\n", i) + 4].replace("struct Sys2Tank {", "struct TankLoopProbe {")
+
+    class PendulumLoopProbe(systems.System):
+        hip_policy = with_members(PENDULUM.replace("PendulumT", "PendulumLoopProbe"), ["LOOP"])
+
+    class PendulumOutLoopProbe(systems.System):
+        hip_policy = with_members(PENDULUM_OUT.replace("PendulumT", "PendulumOutLoopProbe"), ["LOOP", "CRITIC"])
+
+    class TankLoopProbe(systems.System):
+        hip_policy = with_members(tank_src, ["LOOP", "CRITIC"])
+
+    pend = dict(pars=[1.3, 9.81, 0.7], bnds=np.array([[-5.0, 5.0]]), dt=0.05, x0=np.array([2.5, 0.0]), a0=[], tgt=[])
+    tank = dict(pars=[18.4, 24.4, 1.3, 1.0, 0.2], bnds=np.array([[0.0, 1.0]]), dt=0.1, x0=np.array([2.0, -2.0]), a0=[0.5],
+                tgt=np.array([0.5, 0.5]), dy=2, R1=np.diag([10.0, 10.0, 1.0]))
+    c = {"pendulum": dict(pend, cls=PendulumLoopProbe, dy=2, R1=np.diag([10.0, 1.0, 0.1])),
+         "pendulum with out": dict(pend, cls=PendulumOutLoopProbe, dy=3, R1=R1_OUT),
+         "Sys2Tank copy": dict(tank, cls=TankLoopProbe), "Sys2Tank (built-in)": dict(tank, cls=systems.Sys2Tank)}[name]
+    plant = c["cls"](sys_type="diff_eqn", dim_state=2, dim_input=1, dim_output=c["dy"], dim_disturb=1 if "Tank" in name else 0,
+                     pars=c["pars"], ctrl_bnds=c["bnds"])
+    dt = c["dt"]
+    ctrl = controllers.CtrlOptPred(1, c["dy"], mode, ctrl_bnds=c["bnds"], action_init=c["a0"], t0=0, sampling_time=dt, Nactor=5,
+                                   pred_step_size=2 * dt, sys_rhs=plant._state_dyn, sys_out=plant.out, state_sys=c["x0"],
+                                   buffer_size=10, gamma=1, Ncritic=4, critic_period=dt, critic_struct="quad-nomix",
+                                   stage_obj_struct="quadratic", stage_obj_pars=[c["R1"]], observation_target=c["tgt"], opt_iters=30)
+    sim = simulator.Simulator(sys_type="diff_eqn", closed_loop_rhs=plant.closed_loop_rhs, sys_out=plant.out, state_init=c["x0"],
+                              action_init=np.zeros(1), t0=0, t1=1e9, dt=dt / 2, max_step=dt / 2, first_step=1e-6, atol=1e-5,
+                              rtol=1e-3, is_disturb=0, is_dyn_ctrl=0)
+    return plant, ctrl, sim
+
+
+def loop_rate(name, mode, fuse, steps):
+    """tools/b1_profile.py's bracket: the calls of the reference's loop body in its order, `steps` simulation steps."""
+    from rcognita_amd import controllers
+
+    plant, ctrl, sim = loop_objects(name, mode)
+    sim.fuse = fuse
+    held = np.zeros(1)
+
+    def body(n):
+        for _ in range(n):
+            sim.sim_step()
+            t, _, obs, full = sim.get_sim_step_data()
+            u = controllers.ctrl_selector(t, obs, held, None, ctrl, mode)
+            plant.receive_action(u)
+            ctrl.receive_sys_state(plant._state)
+            ctrl.upd_accum_obj(obs, u)
+            ctrl.stage_obj(obs, u)
+
+    t0 = time.perf_counter()
+    body(20)  # (first use: the loop program of this tree's fused run is compiled here)
+    first = time.perf_counter() - t0
+    t0 = time.perf_counter()
+    body(steps)
+    return steps / (time.perf_counter() - t0), ctrl.fused_steps, first
+
+
+def loop_worker():
+    """Serves `<case index> <fuse 0|1> <steps>` lines on stdin with `<rate> <fused steps> <seconds of the first 20 steps>`."""
+    print("ready", flush=True)
+    for line in sys.stdin:
+        i, fuse, steps = (int(v) for v in line.split())
+        rate, fused, first = loop_rate(*LOOP_CASES[i], bool(fuse), steps)
+        print(f"{rate:.6e} {fused} {first:.3f}", flush=True)
+
+
+def loop_rows(other_root=None, steps=2000, rounds=5):
+    import subprocess
+
+    def worker(root):
+        w = subprocess.Popen([sys.executable, os.path.abspath(__file__), "1", "1", "5", "loop-worker", root], stdin=subprocess.PIPE,
+                             stdout=subprocess.PIPE, text=True, cwd=root)
+        assert w.stdout.readline().strip() == "ready"
+        return w
+
+    def ask(w, i, fuse, n):
+        w.stdin.write(f"{i} {int(fuse)} {n}\n")
+        w.stdin.flush()
+        rate, fused, first = w.stdout.readline().split()
+        return float(rate), int(fused), float(first)
+
+    here = worker(ROOT)
+    there = worker(os.path.abspath(other_root)) if other_root else None
+    ways = [("fused", here, True), ("fuse = False", here, False)] + ([("other checkout", there, True)] if there else [])
+    for i, (name, mode) in enumerate(LOOP_CASES):  # first use: registration, then the loop program with the first fused steps
+        t0 = time.perf_counter()
+        _, fused, first = ask(here, i, True, 20)
+        total = time.perf_counter() - t0
+        _, _, again = ask(here, i, True, 20)
+        print(f"loop {name:22s} {mode}: first 20 fused steps {first:.2f} s (registration and handles before them {total - first:.2f} s), "
+              f"the same again {again:.3f} s: first use of the loop program ~ {first - again:.2f} s; {fused} of 40 steps fused")
+        for _, w, fuse in ways[1:]:
+            ask(w, i, fuse, 20)
+    rates = {(i, tag): [] for i in range(len(LOOP_CASES)) for tag, _, _ in ways}
+    fused_n = {}
+    for _ in range(rounds):  # interleaved: every way of every case in turn
+        for i in range(len(LOOP_CASES)):
+            for tag, w, fuse in ways:
+                r, f, _ = ask(w, i, fuse, steps)
+                rates[(i, tag)].append(r)
+                fused_n[(i, tag)] = f
+    for i, (name, mode) in enumerate(LOOP_CASES):
+        parts = [f"{tag} {np.median(rates[(i, tag)]):.3e} ({min(rates[(i, tag)]):.3e} .. {max(rates[(i, tag)]):.3e}; "
+                 f"{fused_n[(i, tag)]} of {steps + 20} steps fused)" for tag, _, _ in ways]
+        print(f"loop {name:22s} {mode} B = 1, sim steps/s, median of {rounds} (min .. max): " + "; ".join(parts))
+    for w in (here, there):
+        if w:
+            w.stdin.close()
+            w.wait(timeout=60)
+
+
+if ONLY == "loop-worker":
+    loop_worker()
+    sys.exit(0)
+if ONLY == "loop":
+    loop_rows(sys.argv[5] if len(sys.argv) > 5 else None)
+    sys.exit(0)
 if ONLY == "search":
     search_rows()
     sys.exit(0)
