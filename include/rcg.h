@@ -159,9 +159,12 @@ typedef struct rcg_cfg {
   double R2[49];            /* stage_obj_pars[1] (biquadratic only)                               */
   double target[8];         /* observation_target (used iff RCG_FLAG_HAS_TARGET)                  */
   double action_init[4];    /* action applied before the first tick (controllers.py:973-978)      */
-  double w_init[40];        /* w_critic_init (controllers.py:1041-1042: ones)                     */
-  double w_min[40];         /* Wmin / Wmax (controllers.py:1026-1039)                             */
-  double w_max[40];
+  double w_init[40];        /* w_critic_init (controllers.py:1041-1042: ones); the fit starts from - and regularises towards -
+                               clip(w_init, w_min, w_max), so it may lie on or outside the box.  RQL / SQL: each of the first
+                               dim_critic entries must be finite, else rcg_create returns RCG_ERR_BAD_ARG                 */
+  double w_min[40];         /* Wmin / Wmax (controllers.py:1026-1039), per weight.  RQL / SQL: each of the first dim_critic  */
+  double w_max[40];         /* entries must be finite and w_min[i] <= w_max[i], else rcg_create returns RCG_ERR_BAD_ARG;
+                               w_min[i] == w_max[i] is legal and pins weight i to that value                               */
   /* Disturbance model (RCG_FLAG_DISTURB), System.pars_disturb = [sigma, mu, tau] (systems.py:303-306, 337):
    * dq_k/dt = -tau_k (q_k + sigma_k (xi_k + mu_k)) (systems.py:343), xi ~ N(0,1) drawn once per RK4 substep from
    * Philox4x32-10 with counter (env id lo, env id hi, EPISODE_IDX, SUBSTEP_IDX) and key (seed lo, seed hi), env id =

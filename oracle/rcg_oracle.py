@@ -785,12 +785,13 @@ def fit_max_iters(dc: int) -> int:
     return 3 * dc + 10
 
 
-def _chol_solve(H, rhs, floor=0.0):
+def _chol_solve(H, rhs, floor=0.0, trace=None):
     """Solve the SPD system ``H x = rhs`` by an unpivoted root-free Cholesky factorisation ``H = L D L^T`` (unit lower
     ``L``), written out in the same operation order as the HIP kernel (rcg_critic_fit.hpp) so both take the same steps:
     one reciprocal per pivot, no square root and no other division (the kernel is bound by float64 instruction issue and
     a divide or square root costs ten to twenty of them; round 1 used L L^T with 3 m of each per solve).  Pivots are
-    floored at ``floor`` (only reached when rounding makes a pivot of a near-singular H non-positive)."""
+    floored at ``floor`` (only reached when rounding makes a pivot of a near-singular H non-positive).  ``trace`` (a dict):
+    ``trace["pivot_floor"]`` counts the floored pivots."""
     m = H.shape[0]
     L = np.array(H, dtype=np.float64)
     d = np.zeros(m)
@@ -801,6 +802,8 @@ def _chol_solve(H, rhs, floor=0.0):
             dj -= (L[j, k] * L[j, k]) * d[k]
         if not dj > floor:
             dj = floor
+            if trace is not None:
+                trace["pivot_floor"] += 1
         d[j] = dj
         r[j] = 1.0 / dj
         for i in range(j + 1, m):
@@ -824,7 +827,11 @@ def _chol_solve(H, rhs, floor=0.0):
     return x
 
 
-def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
+FIT_TRACE_KEYS = ("iters", "fix_lo", "fix_hi", "release", "zero_step", "blocked", "skip_blocked", "pivot_floor", "mu_floor",
+                  "start_bound", "cap", "safeguard")
+
+
+def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None, trace=None):
     """Bounded least squares of the TD stack for ONE env.
 
     The reference minimises ``Jc(w) = 1/2 |A w - b|^2`` over the box ``[Wmin, Wmax]`` with SLSQP started
@@ -851,7 +858,19 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
     problem is strictly convex), so the start only decides how many iterations the walk takes: the kernel starts from
     the previous fit's weights, whose active set is usually already the optimal one (1-2 iterations instead of one per
     bound the cold walk has to find).
+
+    ``trace`` (a dict, default None: nothing is counted and the arithmetic and its order are what they are without it)
+    receives what the walk did, one counter per branch (``FIT_TRACE_KEYS``): ``iters`` iterations; ``fix_lo`` / ``fix_hi``
+    variables fixed at a bound by the ratio test; ``release`` bound variables released; ``zero_step`` ratio-test steps of
+    length zero; ``blocked`` variables barred from release (pushed straight back by a zero step); ``skip_blocked`` barred
+    variables passed over by the release scan; ``pivot_floor`` Cholesky pivots floored; ``mu_floor`` (0 / 1) mu raised to
+    1e-30; ``start_bound`` (0 / 1) the walk started with a variable on a bound; ``cap`` (0 / 1) the walk ended by the
+    iteration cap, not by optimality; ``safeguard`` (0 / 1) the result was replaced by ``clip(w_init)``.  Also the walk's
+    final active set, ``free`` and ``at_hi`` (bool ``[dc]``, as they stood when the walk ended).
     """
+    if trace is not None:
+        for key in FIT_TRACE_KEYS:
+            trace[key] = 0
     A = np.asarray(A, dtype=np.float64)
     b = np.asarray(b, dtype=np.float64)
     w0 = np.asarray(w0, dtype=np.float64)
@@ -865,6 +884,8 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
     mu = FIT_MU_REL * (tr / m)
     if not mu > 1e-30:
         mu = 1e-30
+        if trace is not None:
+            trace["mu_floor"] = 1
 
     w = np.minimum(np.maximum(w0 if w_start is None else np.asarray(w_start, dtype=np.float64), lo), hi)
     free = (w > lo) & (w < hi)
@@ -873,6 +894,9 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
     last_freed = -1
     z = np.zeros(dc)
     iters = 0
+    optimal = False
+    if trace is not None and not np.all(free):
+        trace["start_bound"] = 1
     for _ in range(fit_max_iters(dc)):
         iters += 1
         rhs = np.zeros(m)
@@ -888,7 +912,7 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
                     if free[i]:
                         acc += A[r, i] * A[q, i]
                 M[r, q] = M[q, r] = acc + (mu if r == q else 0.0)
-        lam = _chol_solve(M, rhs, floor=mu * 1e-6)
+        lam = _chol_solve(M, rhs, floor=mu * 1e-6, trace=trace)
         # ratio test: the step to the bound z_i crosses is a_i = n_i / d_i, n_i = |bound_i - w_i| <= d_i = |z_i - w_i|; the
         # smallest one (first index on ties) is found by cross-multiplication, alpha is the ONE division (as the kernel)
         nb, db, jmin = 2.0, 1.0, -1
@@ -918,6 +942,12 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
                 blocked[:] = False
             elif jmin == last_freed:
                 blocked[jmin] = True
+            if trace is not None:
+                trace["fix_hi" if at_hi[jmin] else "fix_lo"] += 1
+                if not alpha > 0.0:
+                    trace["zero_step"] += 1
+                    if jmin == last_freed:
+                        trace["blocked"] += 1
             last_freed = -1
             continue
         res = -b.copy()
@@ -929,6 +959,8 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
         best, best_score = -1, 0.0
         for i in range(dc):
             if free[i] or blocked[i]:
+                if trace is not None and blocked[i] and not free[i]:
+                    trace["skip_blocked"] += 1
                 continue
             g = mu * (w[i] - w0[i])
             scale = abs(g)
@@ -940,9 +972,12 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
             if score > FIT_KKT_TOL * scale and score > best_score:
                 best, best_score = i, score
         if best < 0:
+            optimal = True
             break
         free[best] = True
         last_freed = best
+        if trace is not None:
+            trace["release"] += 1
     if stats is not None:
         stats.append(iters)
 
@@ -951,18 +986,177 @@ def critic_fit_single(A, b, w0, lo, hi, stats=None, w_start=None):
         return 0.5 * float(r @ r)
 
     wi = np.minimum(np.maximum(w0, lo), hi)
-    return w if primal(w) <= primal(wi) else wi
+    keep = primal(w) <= primal(wi)
+    if trace is not None:
+        trace["iters"] = iters
+        trace["cap"] = 0 if optimal else 1
+        trace["safeguard"] = 0 if keep else 1
+        trace["free"], trace["at_hi"] = free.copy(), at_hi.copy()
+    return w if keep else wi
 
 
-def critic_fit(cfg: OracleCfg, w_prev, obs_buf, act_buf, w_init=None, w_start=None, stats=None):
+def critic_fit(cfg: OracleCfg, w_prev, obs_buf, act_buf, w_init=None, w_start=None, stats=None, lo=None, hi=None, trace=None):
     """Batched wrapper: ``w_prev [B, dc]``, buffers ``[B, buffer_size, d]`` -> fitted ``w [B, dc]``; ``w_start [B, dc]``
-    as in :func:`critic_fit_single`."""
+    as in :func:`critic_fit_single`.  ``lo`` / ``hi`` ``[dc]`` (default: ``critic_bounds``, the reference's box) and
+    ``w_init [dc]`` (default: ones) are the handle's ``w_min`` / ``w_max`` / ``w_init``; ``trace`` (a list) receives one trace
+    dict per env."""
     A, b = critic_td_system(w_prev, obs_buf, act_buf, cfg)
     B = A.shape[0]
-    lo, hi = critic_bounds(cfg.critic_struct, cfg.dc)
+    lo0, hi0 = critic_bounds(cfg.critic_struct, cfg.dc)
+    lo = lo0 if lo is None else np.asarray(lo, dtype=np.float64)
+    hi = hi0 if hi is None else np.asarray(hi, dtype=np.float64)
     w0 = np.ones(cfg.dc) if w_init is None else np.asarray(w_init, dtype=np.float64)
-    return np.stack([critic_fit_single(A[i], b[i], w0, lo, hi, stats=stats,
-                                       w_start=None if w_start is None else np.asarray(w_start)[i]) for i in range(B)])
+    out = []
+    for i in range(B):
+        tr = None
+        if trace is not None:
+            tr = {}
+            trace.append(tr)
+        out.append(critic_fit_single(A[i], b[i], w0, lo, hi, stats=stats,
+                                     w_start=None if w_start is None else np.asarray(w_start)[i], trace=tr))
+    return np.stack(out)
+
+
+class ExactFit:
+    """What :func:`critic_fit_exact` returns: ``w`` the minimiser rounded to float64 ``[dc]``, ``w_mp`` the same as mpmath
+    numbers, ``mu`` (mpmath), ``free`` / ``at_hi`` its active set (bool ``[dc]``; a variable with ``lo == hi`` counts as bound
+    at lo), ``iters`` extended-precision solves it took, and ``objective(v)``: the regularised objective
+    ``F(v) = 1/2 |A v - b|^2 + mu/2 |v - w_init|^2`` of any float64 point in the same extended precision (an mpmath number)."""
+
+    def __init__(self, mp, A, b, w0, mu, w_mp, free, at_hi, iters):
+        self._mp, self._A, self._b, self._w0 = mp, A, b, w0
+        self.mu, self.w_mp, self.free, self.at_hi, self.iters = mu, w_mp, free, at_hi, iters
+        self.w = np.array([float(v) for v in w_mp])
+
+    def objective(self, v):
+        mp = self._mp
+        with mp.workdps(FIT_EXACT_DPS):
+            v = [mp.mpf(float(x)) for x in np.asarray(v, dtype=np.float64)] if not isinstance(v, list) else v
+            F = mp.mpf(0)
+            for row, br in zip(self._A, self._b):
+                r = mp.fdot(row, v) - br
+                F += r * r
+            d = [x - y for x, y in zip(v, self._w0)]
+            return (F + self.mu * mp.fdot(d, d)) / 2
+
+
+FIT_EXACT_DPS = 50      # decimal digits of the extended-precision reference
+FIT_EXACT_TOL = 1e-30   # its KKT conditions hold to this, relative to the sum of the gradient's absolute terms
+
+
+def critic_fit_exact(A, b, w0, lo, hi, guess=None):
+    """THE minimiser of ``1/2 |A w - b|^2 + mu/2 |w - w0|^2`` over ``lo <= w <= hi`` (``mu = FIT_MU_REL trace(A A^T) / m``,
+    floored at 1e-30 - the problem :func:`critic_fit_single` defines) in ``FIT_EXACT_DPS``-digit arithmetic (mpmath), for ONE
+    env.  ``A, b, w0, lo, hi`` are float64 and enter exactly.
+
+    Method: a primal active-set walk like the float64 one, but every number in extended precision and with no float64
+    safeguards (no blocked set, no pivot floor, no iteration cap short of ``20 dc + 50``).  It starts from ``guess = (free,
+    at_hi)`` - by default the active set the float64 walk ended on, which is nearly always the optimal one, so that one
+    solve and one check is the whole cost - and from the feasible point that has the guess's bound variables on their bounds
+    and the others where the float64 walk left them (``clip(w0)`` with an explicit guess).  The problem is strictly convex (``mu > 0``), so a feasible point that satisfies the KKT
+    conditions is the unique minimiser whatever path led to it: before returning, the function verifies, in extended
+    precision and relative to the sum of each gradient component's absolute terms, that free variables have a zero gradient
+    (``FIT_EXACT_TOL``), that every variable lies in its box, and that a variable on its lower (upper) bound has a gradient
+    that is not negative (positive) beyond ``FIT_EXACT_TOL`` - a variable with ``lo == hi`` has no sign condition.  Raises
+    ``ArithmeticError`` if the walk does not end or the verification fails.  Returns an :class:`ExactFit`."""
+    import mpmath
+
+    mp = mpmath.mp
+    A64 = np.asarray(A, dtype=np.float64)
+    m, dc = A64.shape
+    lo64, hi64 = np.asarray(lo, dtype=np.float64), np.asarray(hi, dtype=np.float64)
+    if not (np.all(np.isfinite(A64)) and np.all(np.isfinite(b)) and np.all(lo64 <= hi64)):
+        raise ArithmeticError("critic_fit_exact: non-finite stack or empty box")
+    start = np.clip(np.asarray(w0, dtype=np.float64), lo64, hi64)
+    if guess is None:
+        tr = {}
+        start = critic_fit_single(A64, b, w0, lo64, hi64, trace=tr)
+        guess = (tr["free"], tr["at_hi"])
+    with mp.workdps(FIT_EXACT_DPS):
+        f = mp.mpf
+        Am = [[f(float(v)) for v in row] for row in A64]
+        At = [[Am[r][i] for r in range(m)] for i in range(dc)]  # columns
+        bm = [f(float(v)) for v in np.asarray(b, dtype=np.float64)]
+        w0m = [f(float(v)) for v in np.asarray(w0, dtype=np.float64)]
+        lom, him = [f(float(v)) for v in lo64], [f(float(v)) for v in hi64]
+        mu = f(FIT_MU_REL) * (sum(mp.fdot(row, row) for row in Am) / m)
+        if not mu > f(1e-30):
+            mu = f(1e-30)
+        pinned = [lom[i] == him[i] for i in range(dc)]
+        free = [bool(guess[0][i]) and not pinned[i] for i in range(dc)]
+        at_hi = [bool(guess[1][i]) and not free[i] and not pinned[i] for i in range(dc)]
+        # (a guessed-free variable whose start sits on a bound is free all the same: its first step decides)
+        w = [f(float(start[i])) if free[i] else (him[i] if at_hi[i] else lom[i]) for i in range(dc)]
+        tol = f(FIT_EXACT_TOL)
+
+        def grad(v):
+            res = [mp.fdot(Am[r], v) - bm[r] for r in range(m)]
+            g, sc = [], []
+            for i in range(dc):
+                t0 = mu * (v[i] - w0m[i])
+                g.append(mp.fdot(At[i], res) + t0)
+                sc.append(mp.fsum([abs(At[i][r] * res[r]) for r in range(m)]) + abs(t0))
+            return g, sc
+
+        iters = 0
+        for _ in range(20 * dc + 50):
+            iters += 1
+            F = [i for i in range(dc) if free[i]]
+            # (A_F A_F^T + mu I) lam = b - A_B w_B - A_F w0_F,  z_F = w0_F + A_F^T lam
+            wb = [w0m[i] if free[i] else w[i] for i in range(dc)]
+            rhs = mp.matrix([bm[r] - mp.fdot(Am[r], wb) for r in range(m)])
+            AF = [[Am[r][i] for i in F] for r in range(m)]
+            M = mp.matrix(m, m)
+            for r in range(m):
+                for q in range(r + 1):
+                    M[r, q] = M[q, r] = mp.fdot(AF[r], AF[q]) + (mu if r == q else 0)
+            lam = list(mp.cholesky_solve(M, rhs))
+            z = list(w)
+            for i in F:
+                z[i] = w0m[i] + mp.fdot(At[i], lam)
+            # ratio test, exact
+            alpha, jmin = None, -1
+            for i in F:
+                if z[i] < lom[i] or z[i] > him[i]:
+                    a = abs((lom[i] if z[i] < lom[i] else him[i]) - w[i]) / abs(z[i] - w[i])
+                    if alpha is None or a < alpha:
+                        alpha, jmin = a, i
+            if jmin >= 0:
+                for i in F:
+                    w[i] = min(max(w[i] + alpha * (z[i] - w[i]), lom[i]), him[i])
+                at_hi[jmin] = z[jmin] > him[jmin]
+                w[jmin] = him[jmin] if at_hi[jmin] else lom[jmin]
+                free[jmin] = False
+                continue
+            w = z
+            g, sc = grad(w)
+            best, best_score = -1, f(0)
+            for i in range(dc):
+                if free[i] or pinned[i]:
+                    continue
+                score = g[i] if at_hi[i] else -g[i]
+                if score > tol * sc[i] and score > best_score:
+                    best, best_score = i, score
+            if best < 0:
+                break
+            free[best] = True
+        else:
+            raise ArithmeticError("critic_fit_exact: the extended-precision walk did not end")
+        # the KKT conditions, verified on the point that is returned
+        g, sc = grad(w)
+        for i in range(dc):
+            if not (lom[i] <= w[i] <= him[i]):
+                raise ArithmeticError(f"critic_fit_exact: variable {i} outside its box")
+            if pinned[i]:
+                continue
+            on_lo, on_hi = w[i] == lom[i], w[i] == him[i]
+            if not on_lo and not on_hi and abs(g[i]) > tol * sc[i]:
+                raise ArithmeticError(f"critic_fit_exact: gradient of free variable {i} is {mp.nstr(g[i], 5)}")
+            if on_lo and g[i] < -tol * sc[i]:
+                raise ArithmeticError(f"critic_fit_exact: multiplier of variable {i} on its lower bound has the wrong sign")
+            if on_hi and g[i] > tol * sc[i]:
+                raise ArithmeticError(f"critic_fit_exact: multiplier of variable {i} on its upper bound has the wrong sign")
+        return ExactFit(mp, Am, bm, w0m, mu, w, np.array(free), np.array(at_hi), iters)
 
 
 def control_tick_opt(cfg: OracleCfg, env: EnvBatch, iters: int, warm_start: bool = False, action_init=None,

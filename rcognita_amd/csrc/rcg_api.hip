@@ -2,6 +2,7 @@
 // per-system launchers (rcg_sys_inst.hip via SysVTable) and the system-independent kernels.
 //
 // There is no CPU fallback in this library: without a HIP device rcg_create fails with RCG_ERR_NO_DEVICE.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
@@ -296,6 +297,19 @@ int rcg_create(const rcg_cfg* cfg, rcg_handle** out) {
   if (cfg->buffer_size < 0) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: buffer_size < 0");
   if (cfg->mode != RCG_MODE_MPC && cfg->buffer_size < 2)
     return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: RQL/SQL need buffer_size >= 2");
+  // the critic's box and start point (RQL / SQL; an MPC handle never reads them): the fit's walk compares against them and clips
+  // into them - a non-finite entry or an empty interval has no minimiser to walk to.  w_min == w_max pins a weight and is legal.
+  if (cfg->mode != RCG_MODE_MPC) {
+    const int dc = dim_critic(cfg->critic_struct, rd.dy, du);
+    for (int i = 0; i < dc; ++i) {
+      if (!std::isfinite(cfg->w_init[i]))
+        return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: w_init[%d] is not finite", i);
+      if (!std::isfinite(cfg->w_min[i])) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: w_min[%d] is not finite", i);
+      if (!std::isfinite(cfg->w_max[i])) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: w_max[%d] is not finite", i);
+      if (cfg->w_min[i] > cfg->w_max[i])
+        return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_create: w_min[%d] = %g > w_max[%d] = %g", i, cfg->w_min[i], i, cfg->w_max[i]);
+    }
+  }
 
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1)
