@@ -15,8 +15,13 @@
 // (none: optimal).  Feasible and monotone, so the result is never worse than w_init.  This mirrors
 // oracle/rcg_oracle.py::critic_fit_single statement by statement; all arithmetic is float64 whatever
 // the handle's dtype (the systems are tiny - m <= 8, dc <= 35 - and badly scaled).  The active set is
-// held in 64-bit lane-private masks and every loop over variables is unrolled with a predicate, so no
+// held in lane-private masks and every loop over variables is unrolled with a predicate, so no
 // array is indexed dynamically.
+//
+// The walk is stated ONCE, critic_walk below, for every fit kernel - k_critic_fit<.., 3> and <.., 8> here, k_critic_fit_ml
+// (rcg_critic_fit_ml.hpp), k_critic_fit_gen (rcg_critic_fit_gen.hpp) and the critic phase of k_ticks_mem (rcg_ticks.hpp) -
+// under two policies: Lanes (one lane per env or four) and Stack (registers with a compile-time row count, or the HBM scratch
+// with a run-time one); see the comment in front of FitOneLane.
 //
 // Cost (profiles/r02_*; tools/critic_fit_probe.py): 10 us per launch at B = 131072 while the oldest buffer rows are still
 // zeros, 56-62 us in the steady state of an RQL closed loop (quadratic critic, m = 3): ~7000 VALU instructions per wave of
@@ -96,43 +101,80 @@ struct FitArgs {
   int ring;
 };
 
-// The part of an env's critic update that precedes the solver: [env step] -> [push] -> TD stack (A, b) and the box.  `store`:
-// this lane writes the env's state / buffers back (false for the lanes that only help with the env's solve, k_critic_fit_ml).
-// Returns false when there is nothing to fit (F.do_fit == 0).
-// (`row(r, phi)` receives the regressor of TD row r, r < m: the one-lane kernels keep all of it - critic_prologue below -, the
-// four-lane kernel only the columns of the calling lane, so that no lane ever holds the whole m x dc stack in registers)
-template <typename Sys, typename real, int CS, int MAXM, typename RowSink>
-__device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
-                                                     const long b, const bool store, double (&bv)[MAXM], RowSink row) {
-  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, DC = CriticDim<CS, DY, DU>::value;
+// A loop over TD rows (or the entries of the m x m factor), i = lo .. hi - 1.  N > 0: the stack is in registers, N bounds hi at
+// compile time and the loop is unrolled in full as N predicated steps - no register array may be indexed at run time, and a
+// bound that depends on an enclosing loop's index must not keep this one from unrolling; N == 0: a plain loop.
+#define RCG_FIT_INL __attribute__((always_inline))
+template <int N, typename Fn>
+__device__ __forceinline__ void fit_for(const int lo, const int hi, Fn f) {
+  if constexpr (N > 0) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+      if (i >= lo && i < hi) f(i);
+  } else {
+    for (int i = lo; i < hi; ++i) f(i);
+  }
+}
+template <int N, typename Fn>
+__device__ __forceinline__ void fit_for_down(const int hi, const int lo, Fn f) {  // i = hi - 1 .. lo
+  if constexpr (N > 0) {
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i)
+      if (i >= lo && i < hi) f(i);
+  } else {
+    for (int i = hi - 1; i >= lo; --i) f(i);
+  }
+}
+
+// The part of an env's critic update that precedes the solver, in its two jobs: critic_step_push - [env step] -> [push] - and
+// critic_td_stack - the TD stack (A, b) from the oldest buffer rows.
+
+// rows of the pushed buffers that stay in registers for the TD stack (logical rows 0 .. KEEP - 1 once the push is done)
+__host__ __device__ constexpr int fit_keep_rows(int maxm) { return maxm + 1 <= 4 ? maxm + 1 : 4; }
+
+// what critic_step_push leaves for critic_td_stack: the TD target weights and the kept rows
+template <typename real, int DC, int DY, int DU, int KEEP>
+struct CriticKept {
+  real wpr[DC];
+  real ko[KEEP][DY], ka[KEEP][DU];
+};
+
+// physical row of the row that is logical row r once this call's push is done (FitArgs::ring)
+template <typename real>
+__device__ __forceinline__ int critic_phys_row(const FitArgs<real>& F, const KParams<real>& Pr, const int r) {
+  if (!F.ring) return r;
+  const int p = F.ring + r;
+  return p >= Pr.buffer_size ? p - Pr.buffer_size : p;
+}
+
+// [env step] -> [push].  `store`: this lane writes the env's state / buffers back (false for the lanes that only help with the
+// env's solve, k_critic_fit_ml).
+template <typename Sys, typename real, int CS, int KEEP>
+__device__ __forceinline__ void critic_step_push(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
+                                                 const long b, const bool store,
+                                                 CriticKept<real, CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value, sys_dy<Sys>(), Sys::DU, KEEP>& K) {
+  constexpr int DS = Sys::DS, DY = sys_dy<Sys>(), DU = Sys::DU, DC = CriticDim<CS, DY, DU>::value;
   constexpr bool OUT = HasOut<Sys>::value;  // the buffers hold observations y = out(x): [buffer_size][DY][B]
-  // rows of the shifted buffers that stay in registers for the TD stack: new row r = old row r + 1, r = 0 .. KEEP - 1
-  constexpr int KEEP = MAXM + 1 <= 4 ? MAXM + 1 : 4;
   const long B = P.B;
-  const int m = P.n_critic - 1;  // rows of the TD stack, 1 <= m <= MAXM (checked on the host)
   const int bs = Pr.buffer_size;
 
   // ---- every load the prologue needs is requested here, before any arithmetic: the env step, the shift of the two
   // buffers and the TD stack used to be three dependent round trips to memory (and the row-by-row shift one per row:
   // the compiler cannot prove that the store to row r leaves row r + 2 alone) ----------------------------------------
-  real wpr[DC];
+  real (&wpr)[DC] = K.wpr;
   if (F.do_fit) {
 #pragma unroll
     for (int i = 0; i < DC; ++i) wpr[i] = F.w_prev[(long)i * B + b];
   }
-  real ko[KEEP][DY], ka[KEEP][DU];  // do_push: old rows 1 .. KEEP (= new rows 0 .. KEEP - 1); else rows 0 .. KEEP - 1
+  // do_push: old rows 1 .. KEEP (= new rows 0 .. KEEP - 1); else rows 0 .. KEEP - 1
+  real (&ko)[KEEP][DY] = K.ko;
+  real (&ka)[KEEP][DU] = K.ka;
   const int koff = F.do_push ? 1 : 0;
   const int ring = F.ring;  // > 0: ring mode (with do_push)
-  // physical row of the row that is logical row r once this call's push is done
-  auto phys = [&](int r) -> int {
-    if (!ring) return r;
-    const int p = ring + r;
-    return p >= bs ? p - bs : p;
-  };
 #pragma unroll
   for (int k = 0; k < KEEP; ++k)
     if (k + koff < bs) {
-      const int pr = ring ? phys(k) : k + koff;
+      const int pr = ring ? critic_phys_row(F, Pr, k) : k + koff;
 #pragma unroll
       for (int c = 0; c < DY; ++c) ko[k][c] = F.obs_buf[((long)pr * DY + c) * B + b];
 #pragma unroll
@@ -179,13 +221,13 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
 #pragma unroll
       for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)(ring - 1) * DU + c) * B + b] = ua[c];
 #pragma unroll
-      for (int k = 0; k < KEEP; ++k)
-        if (k == bs - 1) {
+      for (int k = 0; k < KEEP; ++k) {
+        const bool newest = k == bs - 1;
 #pragma unroll
-          for (int c = 0; c < DY; ++c) ko[k][c] = ys[c];
+        for (int c = 0; c < DY; ++c) ko[k][c] = newest ? ys[c] : ko[k][c];
 #pragma unroll
-          for (int c = 0; c < DU; ++c) ka[k][c] = ua[c];
-        }
+        for (int c = 0; c < DU; ++c) ka[k][c] = newest ? ua[c] : ka[k][c];
+      }
     } else if (F.do_push) {  // push_vec on both buffers: drop row 0, append (obs, action_curr) at the bottom (utilities.py:78-79)
 #pragma unroll
       for (int k = 0; k < KEEP; ++k)
@@ -221,82 +263,65 @@ __device__ __forceinline__ bool critic_prologue_rows(const FitArgs<real>& F, con
 #pragma unroll
       for (int c = 0; c < DU; ++c) if (store) F.act_buf[((long)(bs - 1) * DU + c) * B + b] = ua[c];
 #pragma unroll
-      for (int k = 0; k < KEEP; ++k)
-        if (k == bs - 1) {  // (buffer_size <= KEEP: the row just pushed is one of the kept rows)
+      for (int k = 0; k < KEEP; ++k) {  // (buffer_size <= KEEP: the row just pushed is one of the kept rows; a select, so that the index stays static)
+        const bool newest = k == bs - 1;
 #pragma unroll
-          for (int c = 0; c < DY; ++c) ko[k][c] = ys[c];
+        for (int c = 0; c < DY; ++c) ko[k][c] = newest ? ys[c] : ko[k][c];
 #pragma unroll
-          for (int c = 0; c < DU; ++c) ka[k][c] = ua[c];
-        }
-    }
-    if (!F.do_fit) return false;
-  }
-
-#pragma unroll
-  for (int r = 0; r < MAXM; ++r) bv[r] = 0.0;
-  // ---- build A, b from buffer rows 0 .. m (the oldest rows, controllers.py:1231-1234) ----------
-#pragma unroll
-  for (int r = 0; r <= MAXM; ++r) {
-    if (r <= m) {
-      double y[DY], u[DU], chi[NCHI], phi[DC];
-      if (r < KEEP) {
-#pragma unroll
-        for (int c = 0; c < DY; ++c) y[c] = (double)ko[r][c];
-#pragma unroll
-        for (int c = 0; c < DU; ++c) u[c] = (double)ka[r][c];
-      } else {  // m > 3: beyond the kept rows (written above by this lane: same-address order, served by L2)
-        const int pr = phys(r);
-#pragma unroll
-        for (int c = 0; c < DY; ++c) y[c] = (double)F.obs_buf[((long)pr * DY + c) * B + b];
-#pragma unroll
-        for (int c = 0; c < DU; ++c) u[c] = (double)F.act_buf[((long)pr * DU + c) * B + b];
-      }
-      if (P.has_target)
-        make_chi<DY, DU, true, double>(P, y, u, chi);
-      else
-        make_chi<DY, DU, false, double>(P, y, u, chi);
-      critic_phi<CS, DY, DU>(chi, y, u, phi);
-      if (r > 0) {  // gamma * w_prev . phi(row r) belongs to TD row r - 1
-        double q = 0.0;
-#pragma unroll
-        for (int i = 0; i < DC; ++i) q = fma_r((double)wpr[i], phi[i], q);
-        bv[r - 1 < MAXM ? r - 1 : 0] += P.gamma * q;
-      }
-      if (r < m && r < MAXM) {
-        row(r, phi);
-        bv[r] += stage_any<NCHI, double>(P, chi);
+        for (int c = 0; c < DU; ++c) ka[k][c] = newest ? ua[c] : ka[k][c];
       }
     }
   }
-
-  return true;
 }
 
-// the whole stack A [m][dc] (rows >= m zero), b, and the box: what the one-lane walks work on
-template <typename Sys, typename real, int CS, int MAXM>
-__device__ __forceinline__ bool critic_prologue(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
-                                                const long b, const bool store,
-                                                double (&A)[MAXM][CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value], double (&bv)[MAXM],
-                                                double (&w0)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value],
-                                                double (&lo)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value],
-                                                double (&hi)[CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value]) {
-  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
+// The TD stack from buffer rows 0 .. m (the oldest rows, controllers.py:1231-1234): rows below KEEP come from the kept
+// registers, the others from the buffers (written by this lane's push: same-address order, served by L2).  The stack receives
+// them: S.put_row(r, phi, rho) stores the regressor of TD row r < m and sets b[r] = rho(y_r, u_r); S.add_target(r, v) adds
+// gamma * w_prev . phi(row r + 1) to b[r].  (The register stacks bound r by their compile-time row count, unrolled.)
+template <typename Sys, typename real, int CS, int KEEP, typename Stack>
+__device__ __forceinline__ void critic_td_stack(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
+                                                const long b,
+                                                const CriticKept<real, CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value, sys_dy<Sys>(), Sys::DU, KEEP>& K,
+                                                Stack& S) {
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU, DC = CriticDim<CS, DY, DU>::value;
+  const long B = P.B;
+  const int m = P.n_critic - 1;  // rows of the TD stack, >= 1 (and <= the register stacks' row count: checked on the host)
+  auto td_row = [&](const int r, const double (&y)[DY], const double (&u)[DU]) RCG_FIT_INL {
+    double chi[NCHI], phi[DC];
+    if (P.has_target)
+      make_chi<DY, DU, true, double>(P, y, u, chi);
+    else
+      make_chi<DY, DU, false, double>(P, y, u, chi);
+    critic_phi<CS, DY, DU>(chi, y, u, phi);
+    if (r > 0) {  // gamma * w_prev . phi(row r) belongs to TD row r - 1
+      double q = 0.0;
 #pragma unroll
-  for (int r = 0; r < MAXM; ++r)
+      for (int i = 0; i < DC; ++i) q = fma_r((double)K.wpr[i], phi[i], q);
+      S.add_target(r - 1, P.gamma * q);
+    }
+    if (r < m) S.put_row(r, phi, stage_any<NCHI, double>(P, chi));
+  };
 #pragma unroll
-    for (int i = 0; i < DC; ++i) A[r][i] = 0.0;
-  const bool fit = critic_prologue_rows<Sys, real, CS, MAXM>(F, P, Pr, b, store, bv, [&](int r, const double (&phi)[DC]) {
+  for (int r = 0; r < KEEP; ++r)
+    if (r <= m) {
+      double y[DY], u[DU];
 #pragma unroll
-    for (int i = 0; i < DC; ++i) A[r][i] = phi[i];
+      for (int c = 0; c < DY; ++c) y[c] = (double)K.ko[r][c];
+#pragma unroll
+      for (int c = 0; c < DU; ++c) u[c] = (double)K.ka[r][c];
+      td_row(r, y, u);
+    }
+  fit_for<(Stack::NROWS > 0 ? Stack::NROWS + 1 : 0)>(KEEP, S.rows() + 1, [&](const int r) RCG_FIT_INL {
+    if (r <= m) {
+      double y[DY], u[DU];
+      const int pr = critic_phys_row(F, Pr, r);
+#pragma unroll
+      for (int c = 0; c < DY; ++c) y[c] = (double)F.obs_buf[((long)pr * DY + c) * B + b];
+#pragma unroll
+      for (int c = 0; c < DU; ++c) u[c] = (double)F.act_buf[((long)pr * DU + c) * B + b];
+      td_row(r, y, u);
+    }
   });
-  if (!fit) return false;
-#pragma unroll
-  for (int i = 0; i < DC; ++i) {
-    w0[i] = F.wcfg[i];
-    lo[i] = F.wcfg[40 + i];
-    hi[i] = F.wcfg[80 + i];
-  }
-  return true;
 }
 
 // After `pushes` ring-mode pushes physical row p of env b holds logical row (p - pushes) mod buffer_size: rotate both buffers left by
@@ -342,206 +367,338 @@ __device__ __forceinline__ void critic_ring_unrotate(const FitArgs<real>& F, con
   }
 }
 
-// Everything of one env, lane-private: [env step] -> [push] -> [fit], in and out through the handle's tensors.  The body of
-// k_critic_fit (lane == env) and of the critic phase of k_ticks_mem (rcg_ticks.hpp: the lanes that stand for the wave's envs).
-template <typename Sys, typename real, int CS, int MAXM>
-__device__ __forceinline__ void critic_update_env(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
-                                                  const long b) {
-  constexpr int DC = CriticDim<CS, sys_dy<Sys>(), Sys::DU>::value;
-  const long B = P.B;
-  const int m = P.n_critic - 1;  // rows of the TD stack, 1 <= m <= MAXM (checked on the host)
-  double A[MAXM][DC], bv[MAXM], w0[DC], lo[DC], hi[DC];
-  if (!critic_prologue<Sys, real, CS, MAXM>(F, P, Pr, b, true, A, bv, w0, lo, hi)) return;
+// ---------------------------------------------------------------------------------------------
+// The walk: ONE statement of it, critic_walk, behind every fit kernel; two small policies say what differs.
+//
+// Lanes - how many lanes share an env.  Slot k of lane s holds variable k * LANES + s, NV = ceil(dc / LANES) slots per lane (a slot
+//   beyond dc: a variable fixed at 0 with a zero column - it never moves).  A sum over the variables is end(partial, x), the
+//   partial begun at start(x); sum(partial) is the same without a first term.  The two decisions of an iteration - the first
+//   bound hit, the most wrong-signed multiplier - end in first() / largest() over the env's lanes.  A mask bit is changed by
+//   the lane that owns the slot.  FitOneLane below; FitFourLanes in rcg_critic_fit_ml.hpp.
+// Stack - where A, b, the factor and the m-vectors live, and where w_init and the box come from: a(r, k), b(r), L(r, q),
+//   lam(r), dg(r), rc(r), res(r), w0(k), lo(k), hi(k); rows() and NROWS say how its row loops run (fit_for); over_rows() runs
+//   the per-variable sums over the rows - r ascending for every variable, the loop order the stack's own.  FitRegStack below
+//   (compile-time row count, rows >= m exact zeros, everything unrolled); FitScratchStack in rcg_critic_fit_gen.hpp.
+// The association of every sum is each form's own and is part of what it computes: a form keeps its bits.
+// ---------------------------------------------------------------------------------------------
+struct FitOneLane {
+  static constexpr int LANES = 1;
+  static constexpr int s = 0;
+  typedef unsigned long long mask_t;  // (up to 35 variables)
+  __device__ __forceinline__ static double start(const double x) { return x; }
+  __device__ __forceinline__ static double end(const double partial, const double) { return partial; }
+  __device__ __forceinline__ static double sum(const double partial) { return partial; }
+  __device__ __forceinline__ static void first(double&, double&, int&) {}
+  __device__ __forceinline__ static void largest(double&, int&) {}
+};
 
-  double tr = 0.0;
-#pragma unroll
-  for (int r = 0; r < MAXM; ++r)
-#pragma unroll
-    for (int i = 0; i < DC; ++i) tr = fma_r(A[r][i], A[r][i], tr);  // rows >= m are zero
-  double mu = FIT_MU_REL * (tr / (double)m);
-  if (!(mu > 1e-30)) mu = 1e-30;
+// The stack of the exact-m kernels, in registers: this lane's NV columns of A [MAXM][dc] (rows >= m zero), b, the factor, and
+// its slots of w_init and the box.
+template <int MAXM, int DC, typename Lanes>
+struct FitRegStack {
+  static constexpr int NROWS = MAXM;  // (compile-time row count)
+  static constexpr int NV = (DC + Lanes::LANES - 1) / Lanes::LANES;
+  const Lanes Ln;
+  // the arrays are the caller's, one object each (critic_update_env): the compiler turns each into registers as soon as ITS
+  // loops are unrolled; as members of one object they would all wait for the deepest nest of the solve
+  double (&A_)[MAXM][NV], (&b_)[MAXM], (&w0_)[NV], (&lo_)[NV], (&hi_)[NV];
+  double (&L_)[MAXM][MAXM], (&lam_)[MAXM], (&dg_)[MAXM], (&rc_)[MAXM], (&res_)[MAXM];
 
-  double w[DC], z[DC];
-  unsigned long long fm = 0ull, at_hi = 0ull, blocked = 0ull;  // free / fixed-at-upper / not-to-release masks
-#pragma unroll
-  for (int i = 0; i < DC; ++i) {
-    w[i] = w0[i] < lo[i] ? lo[i] : (w0[i] > hi[i] ? hi[i] : w0[i]);
-    z[i] = w[i];
-    if (w[i] > lo[i] && w[i] < hi[i])
-      fm |= 1ull << i;
-    else if (w[i] >= hi[i])
-      at_hi |= 1ull << i;
-  }
-  int last_freed = -1;
-
-  // Cost model, measured at B = 131072 (2tank, quadratic critic, steady state of an RQL loop, tools/critic_fit_probe.py
-  // with the walk capped at c iterations): 14 us + 3.6 us x c up to c = 8, 66 us uncapped (the longest walk of the batch):
-  // with B / 64 = 2 waves per SIMD the kernel lasts as long as its slowest wave, and a wave runs as many iterations as
-  // its slowest lane.  Per-variable work is straight-line code on selects and the ratio test divides once; one
-  // iteration is ~680 VALU instructions of which 250 are float64 arithmetic and 160 are the halves of 64-bit selects.
-  // Re-packing unfinished walks into dense waves between levels of iterations (LDS hand-over, blocks of 256 envs) was
-  // built and measured in round 2: 34 % fewer instructions per wave, bit-identical weights, the same duration - dropped.
-  for (int it = 0; it < fit_max_iters(DC); ++it) {
-    // rhs = b - A_B w_B - A_F w0_F,  M = A_F A_F^T + mu I  (rows >= m: M = mu I, rhs = 0 -> lam = 0)
-    double L[MAXM][MAXM], lam[MAXM];
-    // A restricted to the free columns (bound columns zero: adding an exact zero leaves the sums' bits unchanged) and
-    // the point the bound part of the right-hand side is taken at, once per iteration instead of a select per term
-    double Af[MAXM][DC], wb[DC];
-#pragma unroll
-    for (int i = 0; i < DC; ++i) {
-      const bool fr = (fm >> i) & 1ull;
-      wb[i] = fr ? w0[i] : w[i];
-#pragma unroll
-      for (int r = 0; r < MAXM; ++r) Af[r][i] = fr ? A[r][i] : 0.0;
-    }
+  __device__ __forceinline__ FitRegStack(const Lanes ln, double (&A)[MAXM][NV], double (&b)[MAXM], double (&w0)[NV], double (&lo)[NV],
+                                         double (&hi)[NV], double (&L)[MAXM][MAXM], double (&lam)[MAXM], double (&dg)[MAXM],
+                                         double (&rc)[MAXM], double (&res)[MAXM])
+      : Ln(ln), A_(A), b_(b), w0_(w0), lo_(lo), hi_(hi), L_(L), lam_(lam), dg_(dg), rc_(rc), res_(res) {
 #pragma unroll
     for (int r = 0; r < MAXM; ++r) {
-      double s = bv[r];
+      b_[r] = 0.0;
 #pragma unroll
-      for (int i = 0; i < DC; ++i) s = fma_r(-A[r][i], wb[i], s);
-      lam[r] = s;
+      for (int k = 0; k < NV; ++k) A_[r][k] = 0.0;
+    }
+  }
+  // w_init and the box: this lane's slots (an empty slot: zeros)
+  __device__ __forceinline__ void load_box(const double* wcfg) {
 #pragma unroll
-      for (int q = 0; q <= r; ++q) {
+    for (int k = 0; k < NV; ++k) {
+      const bool mine = k * Lanes::LANES + Ln.s < DC;
+      const int i = mine ? k * Lanes::LANES + Ln.s : 0;
+      const double v0 = wcfg[i], vl = wcfg[40 + i], vh = wcfg[80 + i];
+      w0_[k] = mine ? v0 : 0.0;
+      lo_[k] = mine ? vl : 0.0;
+      hi_[k] = mine ? vh : 0.0;
+    }
+  }
+  // critic_td_stack's sink (r runs to MAXM in the unrolled loop: the bound keeps the indices static)
+  __device__ __forceinline__ void put_row(const int r, const double (&phi)[DC], const double rho) {
+    if (r < MAXM) {
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        double v = 0.0;
+#pragma unroll
+        for (int t = 0; t < Lanes::LANES; ++t)
+          if (k * Lanes::LANES + t < DC) v = Ln.s == t ? phi[k * Lanes::LANES + t] : v;
+        A_[r][k] = v;
+      }
+      b_[r] += rho;
+    }
+  }
+  __device__ __forceinline__ void add_target(const int r, const double v) { b_[r < MAXM ? r : 0] += v; }
+
+  __device__ __forceinline__ static constexpr int rows() { return MAXM; }
+  __device__ __forceinline__ double a(const int r, const int k) const { return A_[r][k]; }
+  __device__ __forceinline__ double b(const int r) const { return b_[r]; }
+  __device__ __forceinline__ double& L(const int r, const int q) { return L_[r][q]; }
+  __device__ __forceinline__ double& lam(const int r) { return lam_[r]; }
+  __device__ __forceinline__ double& dg(const int r) { return dg_[r]; }
+  __device__ __forceinline__ double& rc(const int r) { return rc_[r]; }
+  __device__ __forceinline__ double& res(const int r) { return res_[r]; }
+  __device__ __forceinline__ double w0(const int k) const { return w0_[k]; }
+  __device__ __forceinline__ double lo(const int k) const { return lo_[k]; }
+  __device__ __forceinline__ double hi(const int k) const { return hi_[k]; }
+  // acc_k = init(k), then term(r, k, a(r, k), acc_k) for r = 0 .. rows() - 1, then use(k, acc_k): variable by variable
+  template <int NACC, typename Init, typename Term, typename Use>
+  __device__ __forceinline__ void over_rows(Init init, Term term, Use use) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+      double acc[NACC];
+      init(k, acc);
+#pragma unroll
+      for (int r = 0; r < MAXM; ++r) term(r, k, A_[r][k], acc);
+      use(k, acc);
+    }
+  }
+  // trace(A A^T): the row-major trace of this lane's columns, summed over the env's lanes
+  __device__ __forceinline__ double trace() const {
+    double tr = 0.0;
+#pragma unroll
+    for (int r = 0; r < MAXM; ++r)
+#pragma unroll
+      for (int k = 0; k < NV; ++k) tr = fma_r(A_[r][k], A_[r][k], tr);  // rows >= m and empty slots are zero
+    return Ln.sum(tr);
+  }
+};
+
+// The primal active-set walk on the stack S with the regularisation weight mu (floored here), to the safeguard and the store
+// of this lane's weights.  Mirrors oracle/rcg_oracle.py::critic_fit_single statement by statement.
+//
+// Cost model, measured on the one-lane register form at B = 131072 (2tank, quadratic critic, steady state of an RQL loop,
+// tools/critic_fit_probe.py with the walk capped at c iterations): 14 us + 3.6 us x c up to c = 8, 66 us uncapped (the longest
+// walk of the batch): with B / 64 = 2 waves per SIMD the kernel lasts as long as its slowest wave, and a wave runs as many
+// iterations as its slowest lane.  Per-variable work is straight-line code on selects and the ratio test divides once; one
+// iteration is ~680 VALU instructions of which 250 are float64 arithmetic and 160 are the halves of 64-bit selects.
+// Re-packing unfinished walks into dense waves between levels of iterations (LDS hand-over, blocks of 256 envs) was
+// built and measured in round 2: 34 % fewer instructions per wave, bit-identical weights, the same duration - dropped.
+template <int DC, typename real, typename Lanes, typename Stack>
+__device__ __forceinline__ void critic_walk(const FitArgs<real>& F, const long B, const long b, const Lanes Ln, Stack& S, double mu) {
+  constexpr int LN = Lanes::LANES, NV = (DC + LN - 1) / LN;
+  constexpr int NR = Stack::NROWS;
+  typedef typename Lanes::mask_t mask_t;
+  constexpr mask_t one = 1;
+  const int m = S.rows();
+  if (!(mu > 1e-30)) mu = 1e-30;
+  auto var = [&](const int k) RCG_FIT_INL -> int { return k * LN + Ln.s; };  // (var(k) >= DC: an empty slot)
+  // (the box is read into locals before any select on it: a read inside an arm of ?: may be compiled as a branch)
+  auto start_point = [&](const int k) RCG_FIT_INL -> double {
+    const double w0k = S.w0(k), lok = S.lo(k), hik = S.hi(k);
+    return w0k < lok ? lok : (w0k > hik ? hik : w0k);
+  };
+
+  double w[NV], z[NV];
+  mask_t fm = 0, at_hi = 0, blocked = 0;  // free / fixed-at-upper / not-to-release masks over this lane's slots
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const double lok = S.lo(k), hik = S.hi(k);
+    w[k] = start_point(k);
+    z[k] = w[k];
+    if (var(k) < DC) {
+      if (w[k] > lok && w[k] < hik)
+        fm |= one << k;
+      else if (w[k] >= hik)
+        at_hi |= one << k;
+    }
+  }
+  int last_freed = -1;  // variable index (the same in all lanes of the env)
+
+  for (int it = 0; it < fit_max_iters(DC); ++it) {
+    // rhs = b - A_B w_B - A_F w0_F,  M = A_F A_F^T + mu I  (register rows >= m: M = mu I, rhs = 0 -> lam = 0).  A_F = the free
+    // columns, a bound one counting as a zero column: adding an exact zero leaves the sums' bits unchanged
+    fit_for<NR>(0, m, [&](const int r) RCG_FIT_INL {
+      double sp = Ln.start(S.b(r)), ar[NV];
+#pragma unroll
+      for (int k = 0; k < NV; ++k) {
+        const bool fr = (fm >> k) & one;
+        const double a = S.a(r, k);
+        sp = fma_r(-a, fr ? S.w0(k) : w[k], sp);
+        ar[k] = fr ? a : 0.0;
+      }
+      S.lam(r) = Ln.end(sp, S.b(r));
+      fit_for<NR>(0, r + 1, [&](const int q) RCG_FIT_INL {
         double acc = 0.0;
 #pragma unroll
-        for (int i = 0; i < DC; ++i) acc = fma_r(Af[r][i], Af[q][i], acc);
-        L[r][q] = acc + (r == q ? mu : 0.0);
-      }
-    }
+        for (int k = 0; k < NV; ++k) {
+          const bool fr = (fm >> k) & one;
+          const double aq = q == r ? ar[k] : (fr ? S.a(q, k) : 0.0);
+          acc = fma_r(ar[k], aq, acc);
+        }
+        S.L(r, q) = Ln.sum(acc) + (r == q ? mu : 0.0);
+      });
+    });
     // root-free Cholesky M = L D L^T (unit lower L): one reciprocal per pivot, no sqrt, no other division - the kernel is
-    // bound by f64 instruction issue and a divide / square root is 10-20 instructions (round 1: L L^T, 3 m of each)
+    // bound by f64 instruction issue and a divide / square root is 10-20 instructions (round 1: L L^T, 3 m of each).  With
+    // several lanes per env every lane holds the same M: the same solve in each
     const double floor_piv = mu * 1e-6;
-    double dg[MAXM], rc[MAXM];
-#pragma unroll
-    for (int j = 0; j < MAXM; ++j) {
-      double dj = L[j][j];
-#pragma unroll
-      for (int k = 0; k < j; ++k) dj -= (L[j][k] * L[j][k]) * dg[k];
+    fit_for<NR>(0, m, [&](const int j) RCG_FIT_INL {
+      double dj = S.L(j, j);
+      fit_for<NR>(0, j, [&](const int k) RCG_FIT_INL {
+        const double l = S.L(j, k);
+        dj -= (l * l) * S.dg(k);
+      });
       if (!(dj > floor_piv)) dj = floor_piv;
-      dg[j] = dj;
-      rc[j] = 1.0 / dj;
-#pragma unroll
-      for (int i = j + 1; i < MAXM; ++i) {
-        double s = L[i][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= (L[i][k] * L[j][k]) * dg[k];
-        L[i][j] = s * rc[j];
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < MAXM; ++i) {  // forward: L y = rhs
-      double s = lam[i];
-#pragma unroll
-      for (int k = 0; k < i; ++k) s -= L[i][k] * lam[k];
-      lam[i] = s;
-    }
-#pragma unroll
-    for (int i = 0; i < MAXM; ++i) lam[i] = lam[i] * rc[i];  // D z = y
-#pragma unroll
-    for (int i = MAXM - 1; i >= 0; --i) {  // backward: L^T lam = z
-      double s = lam[i];
-#pragma unroll
-      for (int k = i + 1; k < MAXM; ++k) s -= L[k][i] * lam[k];
-      lam[i] = s;
-    }
+      S.dg(j) = dj;
+      const double rcj = 1.0 / dj;
+      S.rc(j) = rcj;
+      fit_for<NR>(j + 1, m, [&](const int i) RCG_FIT_INL {
+        double sv = S.L(i, j);
+        fit_for<NR>(0, j, [&](const int k) RCG_FIT_INL { sv -= (S.L(i, k) * S.L(j, k)) * S.dg(k); });
+        S.L(i, j) = sv * rcj;
+      });
+    });
+    fit_for<NR>(0, m, [&](const int i) RCG_FIT_INL {  // forward: L y = rhs
+      double sv = S.lam(i);
+      fit_for<NR>(0, i, [&](const int k) RCG_FIT_INL { sv -= S.L(i, k) * S.lam(k); });
+      S.lam(i) = sv;
+    });
+    fit_for<NR>(0, m, [&](const int i) RCG_FIT_INL { S.lam(i) = S.lam(i) * S.rc(i); });  // D z = y
+    fit_for_down<NR>(m, 0, [&](const int i) RCG_FIT_INL {  // backward: L^T lam = z
+      double sv = S.lam(i);
+      fit_for<NR>(i + 1, m, [&](const int k) RCG_FIT_INL { sv -= S.L(k, i) * S.lam(k); });
+      S.lam(i) = sv;
+    });
     // z_F = w0_F + A_F^T lam and the ratio test towards it: the step to the bound z_i crosses is a_i = n_i / d_i with
-    // n_i = |bound_i - w_i| <= d_i = |z_i - w_i|; the smallest a_i (first index on ties) is found by comparing
-    // n_i d_best with n_best d_i - no division - and alpha = n_best / d_best is the one division of the iteration
+    // n_i = |bound_i - w_i| <= d_i = |z_i - w_i|; the smallest a_i (lowest variable index on ties) is found by comparing
+    // n_i d_best with n_best d_i - no division - over this lane's slots in index order, then over the env's lanes
+    // (Lanes::first), and alpha = n_best / d_best is the one division of the iteration
     double nb = 2.0, db = 1.0;
     int jmin = -1;
-#pragma unroll
-    for (int i = 0; i < DC; ++i) {
-      const bool fr = (fm >> i) & 1ull;
-      double c = 0.0;
-#pragma unroll
-      for (int r = 0; r < MAXM; ++r) c = fma_r(A[r][i], lam[r], c);
-      const double zi = w0[i] + c;
-      z[i] = fr ? zi : z[i];
-      const bool vlo = zi < lo[i], vhi = zi > hi[i];
-      const double ni = fabs((vlo ? lo[i] : hi[i]) - w[i]), di = fabs(zi - w[i]);
-      if (fr && (vlo || vhi) && ni * db < nb * di) {
-        nb = ni;
-        db = di;
-        jmin = i;
-      }
-    }
-    if (jmin >= 0) {  // move towards z until the first bound, fix that variable
+    S.template over_rows<1>([&](const int, double (&c)[1]) RCG_FIT_INL { c[0] = 0.0; },
+                            [&](const int r, const int, const double a, double (&c)[1]) RCG_FIT_INL { c[0] = fma_r(a, S.lam(r), c[0]); },
+                            [&](const int k, const double (&c)[1]) RCG_FIT_INL {
+                              const bool fr = (fm >> k) & one;
+                              const double lok = S.lo(k), hik = S.hi(k);
+                              const double zi = S.w0(k) + c[0];
+                              z[k] = fr ? zi : z[k];
+                              const bool vlo = zi < lok, vhi = zi > hik;
+                              const double ni = fabs((vlo ? lok : hik) - w[k]), di = fabs(zi - w[k]);
+                              if (fr && (vlo || vhi) && ni * db < nb * di) {
+                                nb = ni;
+                                db = di;
+                                jmin = var(k);
+                              }
+                            });
+    Ln.first(nb, db, jmin);
+    if (jmin >= 0) {  // move towards z until the first bound, fix that variable (its owner does)
       double alpha = nb / db;
       if (!(alpha > 0.0)) alpha = 0.0;
 #pragma unroll
-      for (int i = 0; i < DC; ++i) {
-        const bool fr = (fm >> i) & 1ull;
-        double v = w[i] + alpha * (z[i] - w[i]);
-        v = v < lo[i] ? lo[i] : (v > hi[i] ? hi[i] : v);
-        const bool up = z[i] > hi[i];
-        if (i == jmin) {
-          v = up ? hi[i] : lo[i];
-          at_hi = up ? (at_hi | (1ull << i)) : (at_hi & ~(1ull << i));
+      for (int k = 0; k < NV; ++k) {
+        const bool fr = (fm >> k) & one;
+        const double lok = S.lo(k), hik = S.hi(k);
+        double v = w[k] + alpha * (z[k] - w[k]);
+        v = v < lok ? lok : (v > hik ? hik : v);
+        const bool up = z[k] > hik;
+        if (var(k) == jmin) {
+          v = up ? hik : lok;
+          at_hi = up ? (at_hi | (one << k)) : (at_hi & ~(one << k));
         }
-        w[i] = fr ? v : w[i];
+        w[k] = fr ? v : w[k];
       }
-      fm &= ~(1ull << jmin);
+      const bool owner = (jmin % LN) == Ln.s;
+      if (owner) fm &= ~(one << (jmin / LN));
       if (alpha > 0.0)
-        blocked = 0ull;
-      else if (jmin == last_freed)
-        blocked |= 1ull << jmin;
+        blocked = 0;
+      else if (jmin == last_freed && owner)
+        blocked |= one << (jmin / LN);
       last_freed = -1;
       continue;
     }
-    double res[MAXM];
+    // accept z; the residual, then per variable the multiplier g_i = mu (w_i - w0_i) + sum_r A[r][i] res[r] and its scale;
+    // release the bound variable with the largest wrong-signed one (lowest index on ties: Lanes::largest keeps the first)
 #pragma unroll
-    for (int r = 0; r < MAXM; ++r) res[r] = -bv[r];
+    for (int k = 0; k < NV; ++k) w[k] = ((fm >> k) & one) ? z[k] : w[k];
+    fit_for<NR>(0, m, [&](const int r) RCG_FIT_INL {
+      double sp = Ln.start(-S.b(r));
 #pragma unroll
-    for (int i = 0; i < DC; ++i) {
-      w[i] = ((fm >> i) & 1ull) ? z[i] : w[i];
-#pragma unroll
-      for (int r = 0; r < MAXM; ++r) res[r] = fma_r(A[r][i], w[i], res[r]);
-    }
+      for (int k = 0; k < NV; ++k) sp = fma_r(S.a(r, k), w[k], sp);
+      S.res(r) = Ln.end(sp, -S.b(r));
+    });
     int best = -1;
     double best_score = 0.0;
-#pragma unroll
-    for (int i = 0; i < DC; ++i) {
-      double g = mu * (w[i] - w0[i]);
-      double scale = fabs(g);
-#pragma unroll
-      for (int r = 0; r < MAXM; ++r) {
-        const double t = A[r][i] * res[r];
-        g += t;
-        scale += fabs(t);
-      }
-      const double score = ((at_hi >> i) & 1ull) ? g : -g;
-      if (!(((fm | blocked) >> i) & 1ull) && score > FIT_KKT_TOL * scale && score > best_score) {
-        best = i;
-        best_score = score;
-      }
-    }
+    S.template over_rows<2>([&](const int k, double (&gs)[2]) RCG_FIT_INL {
+                              gs[0] = mu * (w[k] - S.w0(k));
+                              gs[1] = fabs(gs[0]);
+                            },
+                            [&](const int r, const int, const double a, double (&gs)[2]) RCG_FIT_INL {
+                              const double t = a * S.res(r);
+                              gs[0] += t;
+                              gs[1] += fabs(t);
+                            },
+                            [&](const int k, const double (&gs)[2]) RCG_FIT_INL {
+                              const double score = ((at_hi >> k) & one) ? gs[0] : -gs[0];
+                              if (var(k) < DC && !(((fm | blocked) >> k) & one) && score > FIT_KKT_TOL * gs[1] && score > best_score) {
+                                best = var(k);
+                                best_score = score;
+                              }
+                            });
+    Ln.largest(best_score, best);
     if (best < 0) break;
-    fm |= 1ull << best;
+    if ((best % LN) == Ln.s) fm |= one << (best / LN);
     last_freed = best;
   }
 
   // safeguard (non-finite buffers): keep the start point unless Jc(w) <= Jc(w_init)
   double Pw = 0.0, P0 = 0.0;
+  fit_for<NR>(0, m, [&](const int r) RCG_FIT_INL {
+    double sp = Ln.start(-S.b(r)), sp0 = sp;
 #pragma unroll
-  for (int r = 0; r < MAXM; ++r) {
-    double s = -bv[r], s0 = -bv[r];
-#pragma unroll
-    for (int i = 0; i < DC; ++i) {
-      const double wi = w0[i] < lo[i] ? lo[i] : (w0[i] > hi[i] ? hi[i] : w0[i]);
-      s = fma_r(A[r][i], w[i], s);
-      s0 = fma_r(A[r][i], wi, s0);
+    for (int k = 0; k < NV; ++k) {
+      const double a = S.a(r, k);
+      sp = fma_r(a, w[k], sp);
+      sp0 = fma_r(a, start_point(k), sp0);
     }
-    Pw = fma_r(s, s, Pw);
-    P0 = fma_r(s0, s0, P0);
-  }
+    const double sr = Ln.end(sp, -S.b(r)), sr0 = Ln.end(sp0, -S.b(r));
+    Pw = fma_r(sr, sr, Pw);
+    P0 = fma_r(sr0, sr0, P0);
+  });
   const bool keep = Pw <= P0;
 #pragma unroll
-  for (int i = 0; i < DC; ++i) {
-    const double wi = w0[i] < lo[i] ? lo[i] : (w0[i] > hi[i] ? hi[i] : w0[i]);
-    const double v = keep ? w[i] : wi;
-    F.w_critic[(long)i * B + b] = (real)v;
-    F.w_prev[(long)i * B + b] = (real)v;  // w_critic_prev = w_critic (controllers.py:1471)
+  for (int k = 0; k < NV; ++k) {
+    if (var(k) < DC) {
+      const double v = keep ? w[k] : start_point(k);
+      F.w_critic[(long)var(k) * B + b] = (real)v;
+      F.w_prev[(long)var(k) * B + b] = (real)v;  // w_critic_prev = w_critic (controllers.py:1471)
+    }
   }
+}
+
+// Everything of one env: [env step] -> [push] -> [fit], in and out through the handle's tensors, by the env's LANES lanes (this
+// one is lane s of them; lane 0 stores the env's state and buffers).  One lane: the body of k_critic_fit (lane == env) and of
+// the critic phase of k_ticks_mem (rcg_ticks.hpp: the lanes that stand for the wave's envs); four: of k_critic_fit_ml and of
+// k_ticks_mem's four-lane form.  Every lane runs the step, the push and b (the same bits whatever the lanes) but keeps only
+// ITS columns of the regressor rows - round 6: with the whole 3 x 35 stack and three 35-entry box arrays per lane the
+// four-lane kernel needed 256 VGPRs + 134 AGPRs (one wave per SIMD).
+template <typename Sys, typename real, int CS, int MAXM, typename Lanes = FitOneLane>
+__device__ __forceinline__ void critic_update_env(const FitArgs<real>& F, const KParams<double>& P, const KParams<real>& Pr,
+                                                  const long b, const Lanes Ln = Lanes()) {
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, DC = CriticDim<CS, DY, DU>::value, KEEP = fit_keep_rows(MAXM);
+  CriticKept<real, DC, DY, DU, KEEP> K;
+  critic_step_push<Sys, real, CS, KEEP>(F, P, Pr, b, Ln.s == 0, K);
+  if (!F.do_fit) return;
+  constexpr int NV = FitRegStack<MAXM, DC, Lanes>::NV;
+  double A[MAXM][NV], bv[MAXM], w0[NV], lo[NV], hi[NV], L[MAXM][MAXM], lam[MAXM], dg[MAXM], rc[MAXM], res[MAXM];
+  FitRegStack<MAXM, DC, Lanes> S(Ln, A, bv, w0, lo, hi, L, lam, dg, rc, res);
+  critic_td_stack<Sys, real, CS, KEEP>(F, P, Pr, b, K, S);
+  S.load_box(F.wcfg);
+  const int m = P.n_critic - 1;  // rows of the TD stack, 1 <= m <= MAXM (checked on the host)
+  critic_walk<DC, real>(F, P.B, b, Ln, S, FIT_MU_REL * (S.trace() / (double)m));
 }
 
 template <typename Sys, typename real, int CS, int MAXM>
@@ -550,5 +707,7 @@ __global__ __launch_bounds__(64) void k_critic_fit(const FitArgs<real> F, const 
   if (b >= (F.env_hi > 0 ? (long)F.env_hi : P.B)) return;
   critic_update_env<Sys, real, CS, MAXM>(F, P, Pr, b);
 }
+
+#undef RCG_FIT_INL
 
 }  // namespace rcg

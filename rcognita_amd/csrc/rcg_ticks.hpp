@@ -296,8 +296,9 @@ struct TicksMemArgs {
   int every;   // critic_every_ticks (>= 1)
 };
 
-// ML (round 5): the critic structures with >= 20 weights, whose single ticks fit with FOUR LANES PER ENV (k_critic_fit_ml): the
-// wave's envs (G <= 16) take the quads 0 .. G - 1 of the wave for phase 1 - critic_update_env_ml, the body of that kernel.
+// ML (round 5): the critic structures with kFitLanesMinDc weights or more, whose single ticks fit with FOUR LANES PER ENV
+// (k_critic_fit_ml): the wave's envs (G <= 16) take the quads 0 .. G - 1 of the wave for phase 1 - critic_update_env with
+// FitFourLanes, the body of that kernel.
 // STREAM (round 5): the decision phase walks a caller's tensor (actor_wave's streamed form: the wave's tile staged through
 // LDS every tick - at the batch sizes this launch is for the tensor stays in L2 / the Infinity Cache).
 template <typename Sys, typename real, int CS, int MAXM, bool TGT, bool ML = false, bool STREAM = false>
@@ -320,7 +321,7 @@ __global__ __launch_bounds__(256) void k_ticks_mem(const TicksMemArgs<real> M, c
     ring = ring == bs ? 1 : ring + 1;
     if constexpr (ML) {
       if (lane < FIT_L * envs_here)  // (whole quads: the DPP exchanges of the four-lane walk stay inside a quad)
-        critic_update_env_ml<Sys, real, CS, MAXM>(F, P64, P, wave * G + (lane / FIT_L), lane & (FIT_L - 1));
+        critic_update_env<Sys, real, CS, MAXM>(F, P64, P, wave * G + (lane / FIT_L), FitFourLanes(lane & (FIT_L - 1)));
     } else {
       if (lane < envs_here) critic_update_env<Sys, real, CS, MAXM>(F, P64, P, wave * G + lane);
     }

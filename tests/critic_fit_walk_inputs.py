@@ -2,12 +2,13 @@
 oracle/experiments/critic_fit_walk_profile.py: the ONE builder of the critic-fit walk's inputs (``walk_batch``, ``walk_box``), the
 cases, and ``WalkReference`` - the oracle's fit with its traces and the exact minimisers of one (structure, rows, box, dtype).  What
 the inputs are for, and why, is told in tests/test_critic_fit_walk.py."""
+import dataclasses
 import functools
 
 import numpy as np
 
 from oracle import rcg_oracle as O
-from tests.helpers import oracle_cfg, rand_actions, rand_states
+from tests.helpers import engine_cfg, oracle_cfg, rand_actions, rand_states
 
 REAL = {"f32": np.float32, "f64": np.float64}
 
@@ -64,6 +65,27 @@ def walk_box(family, cs, dc):
     elif family != "preset":
         raise ValueError(family)
     return w0, lo, hi
+
+
+NAN_ENVS = (34, 66)  # next to wprev_1e3 envs (33, 65) and near one-iteration envs, in the middle of wave 0 and in the ragged wave 1
+
+
+def boxed_engine(name, B, dtype, cs, m, box, **kw):
+    """Engine whose rcg_cfg carries ``box = (w_init, w_min, w_max)`` instead of the structure's preset."""
+    from rcognita_amd import Engine, EngineConfig
+
+    @dataclasses.dataclass
+    class BoxedConfig(EngineConfig):
+        w_box: tuple = None
+
+        def to_native(self):
+            c = super().to_native()
+            for i, (w0, lo, hi) in enumerate(zip(*self.w_box)):
+                c.w_init[i], c.w_min[i], c.w_max[i] = w0, lo, hi
+            return c
+
+    ec = engine_cfg(name, B, dtype, **dict(walk_cfg_kw(cs, m), **kw))
+    return Engine(BoxedConfig(**{f.name: getattr(ec, f.name) for f in dataclasses.fields(ec)}, w_box=box))
 
 
 def long_walk_env(name, cs, m, seed, equal_from=0):

@@ -108,3 +108,16 @@ def assert_kernel(eng, kernel, variant=None, kind=None):
     if variant is not None:
         assert ll["variant"] == variant, f"expected variant {variant}, the library launched {ll}"
     return ll
+
+
+def load_buffers(eng, N, obs_buf, act_buf, w_prev):
+    """Arrange the handle so that ONE push (rcg_critic_update) leaves exactly (obs_buf, act_buf):
+    rows shifted down by one, the newest row supplied through STATE / ACTION."""
+    B, bs, _ = obs_buf.shape
+    ob = np.concatenate([np.zeros_like(obs_buf[:, :1]), obs_buf[:, :-1]], axis=1)
+    ab = np.concatenate([np.zeros_like(act_buf[:, :1]), act_buf[:, :-1]], axis=1)
+    eng.set_field(N.FIELD_OBS_BUF, ob)
+    eng.set_field(N.FIELD_ACT_BUF, ab)
+    eng.set_field(N.FIELD_STATE, obs_buf[:, -1])
+    eng.set_field(N.FIELD_ACTION, act_buf[:, -1])
+    eng.set_field(N.FIELD_W_PREV, w_prev)

@@ -6,21 +6,9 @@ import pytest
 from oracle import rcg_oracle as O
 from tests.conftest import load_golden
 from tests.helpers import SYSTEMS, assert_kernel, both, rand_actions, rand_states, rel_err_norm
+from tests.helpers import load_buffers as _load_buffers  # (shared with tools/ab_bits.py)
 
 pytestmark = pytest.mark.gpu
-
-
-def _load_buffers(eng, N, obs_buf, act_buf, w_prev):
-    """Arrange the handle so that ONE push (rcg_critic_update) leaves exactly (obs_buf, act_buf):
-    rows shifted down by one, the newest row supplied through STATE / ACTION."""
-    B, bs, _ = obs_buf.shape
-    ob = np.concatenate([np.zeros_like(obs_buf[:, :1]), obs_buf[:, :-1]], axis=1)
-    ab = np.concatenate([np.zeros_like(act_buf[:, :1]), act_buf[:, :-1]], axis=1)
-    eng.set_field(N.FIELD_OBS_BUF, ob)
-    eng.set_field(N.FIELD_ACT_BUF, ab)
-    eng.set_field(N.FIELD_STATE, obs_buf[:, -1])
-    eng.set_field(N.FIELD_ACTION, act_buf[:, -1])
-    eng.set_field(N.FIELD_W_PREV, w_prev)
 
 
 @pytest.mark.parametrize("dtype", ["f64", "f32"])

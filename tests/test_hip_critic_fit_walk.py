@@ -10,39 +10,17 @@ The yardsticks are independent of the walk: feasibility, "never worse than the s
 ``critic_fit_exact`` (the KKT-verified minimiser in 50-digit arithmetic).  The oracle twin is compared in ``w`` only where the
 CPU file's criterion says the minimiser is well separated.  The box and the start point of a handle are fields of ``rcg_cfg``
 that ``EngineConfig.to_native`` fills with the structure's preset; ``BoxedConfig`` overwrites them."""
-import dataclasses
 
 import numpy as np
 import pytest
 
 from oracle import rcg_oracle as O
-from tests.helpers import assert_kernel, engine_cfg, rand_states, rel_err_norm
-from tests.critic_fit_walk_inputs import (B_WALK, BOX_FAMILIES, DC, GAP_FACTOR_DEVICE, GAP_MEASURED, GPU_CASES, REAL,
-                                          STACK_FAMILIES, walk_batch, walk_box, walk_cfg_kw, walk_reference)
+from tests.helpers import assert_kernel, rand_states, rel_err_norm
+from tests.critic_fit_walk_inputs import (B_WALK, BOX_FAMILIES, DC, GAP_FACTOR_DEVICE, GAP_MEASURED, GPU_CASES, NAN_ENVS, REAL,
+                                          STACK_FAMILIES, boxed_engine, walk_batch, walk_box, walk_reference)
 from tests.test_hip_critic import _load_buffers
 
 pytestmark = pytest.mark.gpu
-
-NAN_ENVS = (34, 66)  # next to wprev_1e3 envs (33, 65) and near one-iteration envs, in the middle of wave 0 and in the ragged wave 1
-
-
-def boxed_engine(name, B, dtype, cs, m, box, **kw):
-    """Engine whose rcg_cfg carries ``box = (w_init, w_min, w_max)`` instead of the structure's preset."""
-    from rcognita_amd import Engine, EngineConfig
-
-    @dataclasses.dataclass
-    class BoxedConfig(EngineConfig):
-        w_box: tuple = None
-
-        def to_native(self):
-            c = super().to_native()
-            for i, (w0, lo, hi) in enumerate(zip(*self.w_box)):
-                c.w_init[i], c.w_min[i], c.w_max[i] = w0, lo, hi
-            return c
-
-    ec = engine_cfg(name, B, dtype, **dict(walk_cfg_kw(cs, m), **kw))
-    return Engine(BoxedConfig(**{f.name: getattr(ec, f.name) for f in dataclasses.fields(ec)}, w_box=box))
-
 
 def expected_form(m, dc):
     """(four lanes, any-m, rows of the register instance) of rcg_last_launch's variant word (rcg_sysops.hpp::fit_plan)."""
