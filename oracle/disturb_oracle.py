@@ -134,3 +134,18 @@ def sim_substeps(cfg, env, dcfg: DisturbCfg, n_substeps):
         env.substep_idx = env.substep_idx + np.int32(1)
         if cfg.accum_every_substep:
             env.accum = env.accum + O.stage_obj(env.state, env.action, cfg) * cfg.sampling_time
+
+
+def stepper(dcfg: DisturbCfg):
+    """The disturbed env step in the shape ``rcg_oracle.control_tick(..., sim=)`` takes: the disturbed closed loop is the
+    undisturbed composition with this step in place of ``rcg_oracle.sim_substeps``, nothing else."""
+    return lambda cfg, env, n: sim_substeps(cfg, env, dcfg, n)
+
+
+def episode_reset(cfg, env, dcfg: DisturbCfg, state_init, action_init=None):
+    """Twin of rcg_episode_reset on a handle created with RCG_FLAG_DISTURB: q := disturb_init (or 0), the substep counter
+    := 0, then ``rcg_oracle.episode_reset`` (which advances episode_idx, the third word of the noise counter)."""
+    B, dd = env.state.shape[0], DIM_DISTURB[cfg.sys_id]
+    env.disturb = np.zeros((B, dd)) if dcfg.disturb_init is None else np.tile(dcfg.disturb_init[:dd], (B, 1))
+    env.substep_idx = np.zeros(B, dtype=np.int32)
+    return O.episode_reset(cfg, env, state_init, action_init)

@@ -166,12 +166,13 @@ def lyapunov_endi(x, theta=None):
         return Fc(xNI, eta, th)
 
 
-def control_tick_nominal(cfg, env, gain, m=None, I=None):
+def control_tick_nominal(cfg, env, gain, m=None, I=None, sim=None):
     """Twin of rcg_control_tick_nominal: sim_step -> clipped nominal action of the new state -> accum, step_idx
-    (the reference loop with ``ctrl_mode='nominal'``, presets/main_3wrobot.py:419-429)."""
+    (the reference loop with ``ctrl_mode='nominal'``, presets/main_3wrobot.py:419-429).  ``sim``: the env step, a callable
+    ``(cfg, env, n_substeps)``, default ``rcg_oracle.sim_substeps``."""
     from . import rcg_oracle as O
 
-    O.sim_substeps(cfg, env, cfg.substeps_per_tick)
+    (O.sim_substeps if sim is None else sim)(cfg, env, cfg.substeps_per_tick)
     env.tick_count += 1
     x = env.state
     bn = cfg.ctrl_bnds  # clipped iff ctrl_bnds.any(), as compute_action (controllers.py:1712)

@@ -47,13 +47,18 @@ class TickReport:
 
 
 def check_tick(cfg: O.OracleCfg, env: O.EnvBatch, cand, dev: Dict[str, np.ndarray], tol: float, tie_rel: float = None,
-               report: TickReport = None, resync: bool = True, what: str = "", tol_over: Dict[str, float] = None):
+               report: TickReport = None, resync: bool = True, what: str = "", tol_over: Dict[str, float] = None, sim=None):
     """Advance ``env`` (oracle) by one control tick and compare with the device's post-tick fields
     ``dev = {state, action, best_idx, best_J, accum, step_idx}`` (host arrays, reference shapes).  Raises
-    AssertionError on a mismatch; returns the (possibly re-synchronised) oracle env."""
+    AssertionError on a mismatch; returns the (possibly re-synchronised) oracle env.
+
+    ``sim``: the oracle's env step (``rcg_oracle.control_tick``), e.g. ``disturb_oracle.stepper(dcfg)``; when ``dev`` also
+    holds ``disturb`` and ``substep_idx`` (``device_fields(disturb=True)``), the disturbance state is compared at ``tol`` and
+    the noise counter bit for bit."""
     tie_rel = 4.0 * tol if tie_rel is None else tie_rel
     before = copy.deepcopy(env)
-    J = O.control_tick(cfg, env, cand)
+    step = {} if sim is None else {"sim": sim}  # (only when asked for: tests bind control_tick to a tick of their own, which has no such argument)
+    J = O.control_tick(cfg, env, cand, **step)
     bi = np.asarray(dev["best_idx"])
     flipped = bi != env.best_idx
     if flipped.any():
@@ -65,7 +70,7 @@ def check_tick(cfg: O.OracleCfg, env: O.EnvBatch, cand, dev: Dict[str, np.ndarra
         assert not bad.any(), (f"{what}: best_idx differs from the oracle's without a near-tie for envs "
                                f"{rows[bad][:8]}: J[dev choice] {j_dev[bad][:8]}, J[best] {j_best[bad][:8]}")
         env = before
-        O.control_tick(cfg, env, cand, force_idx=np.where(flipped, bi, -1))
+        O.control_tick(cfg, env, cand, force_idx=np.where(flipped, bi, -1), **step)
     Jf = np.where(np.isfinite(J), J, 0.0)
     jscale = np.maximum(np.max(np.abs(Jf), axis=1), 1e-30)
     errs = {
@@ -80,6 +85,9 @@ def check_tick(cfg: O.OracleCfg, env: O.EnvBatch, cand, dev: Dict[str, np.ndarra
         errs["w_critic"] = rel_err_norm(dev["w_critic"], env.w_critic)
         errs["obs_buf"] = rel_err_norm(dev["obs_buf"], env.obs_buf)
         errs["act_buf"] = rel_err_norm(dev["act_buf"], env.act_buf)
+    if "disturb" in dev and "substep_idx" in dev:  # RCG_FLAG_DISTURB handles
+        errs["disturb"] = rel_err_norm(dev["disturb"], env.disturb, floor=1.0)
+        assert np.array_equal(np.asarray(dev["substep_idx"]), env.substep_idx), f"{what}: substep_idx (int32) must be bit-exact"
     for k, v in errs.items():
         # `tol_over`: per-quantity tolerances, e.g. the critic weights - they solve a least-squares problem regularised
         # at 1e-8 of its scale, so last-bit differences of the two float64 solvers are amplified accordingly - and the
@@ -100,6 +108,8 @@ def check_tick(cfg: O.OracleCfg, env: O.EnvBatch, cand, dev: Dict[str, np.ndarra
         env.accum = np.asarray(dev["accum"], dtype=np.float64).copy()
         if dev.get("state_prev") is not None:
             env.state_prev = np.asarray(dev["state_prev"], dtype=np.float64).copy()
+        if "disturb" in dev and "substep_idx" in dev:
+            env.disturb = np.asarray(dev["disturb"], dtype=np.float64).copy()
         if "w_critic" in dev:
             env.w_critic = np.asarray(dev["w_critic"], dtype=np.float64).copy()
             env.w_prev = np.asarray(dev["w_prev"], dtype=np.float64).copy()
@@ -108,7 +118,7 @@ def check_tick(cfg: O.OracleCfg, env: O.EnvBatch, cand, dev: Dict[str, np.ndarra
     return env
 
 
-def device_fields(eng, N, with_prev=False, critic=False):
+def device_fields(eng, N, with_prev=False, critic=False, disturb=False):
     """Post-tick fields of an ``rcognita_amd.Engine`` in the layout ``check_tick`` expects (``N`` = rcognita_amd._native)."""
     d = {"state": eng.get_state(), "action": eng.get_field(N.FIELD_ACTION), "best_idx": eng.get_field(N.FIELD_BEST_IDX),
          "best_J": eng.get_field(N.FIELD_BEST_J), "accum": eng.get_field(N.FIELD_ACCUM),
@@ -118,4 +128,6 @@ def device_fields(eng, N, with_prev=False, critic=False):
     if critic:
         d.update(w_critic=eng.get_field(N.FIELD_W_CRITIC), w_prev=eng.get_field(N.FIELD_W_PREV),
                  obs_buf=eng.get_field(N.FIELD_OBS_BUF), act_buf=eng.get_field(N.FIELD_ACT_BUF))
+    if disturb:
+        d.update(disturb=eng.get_field(N.FIELD_DISTURB), substep_idx=eng.get_field(N.FIELD_SUBSTEP_IDX))
     return d

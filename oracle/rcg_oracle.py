@@ -449,8 +449,11 @@ def sim_substeps(cfg: OracleCfg, env: EnvBatch, n_substeps: int):
             env.accum = env.accum + stage_obj(env.state, env.action, cfg) * cfg.sampling_time
 
 
-def control_tick(cfg: OracleCfg, env: EnvBatch, cand, force_idx=None):
+def control_tick(cfg: OracleCfg, env: EnvBatch, cand, force_idx=None, sim=None):
     """One env.control-step (unit U2 of SURVEY §8d) for every env of the batch.
+
+    ``sim``: the env step, a callable ``(cfg, env, n_substeps)``; default :func:`sim_substeps` (the disturbed loop passes
+    ``disturb_oracle.stepper(dcfg)``: everything after the step is the same composition).
 
     ``force_idx [B]`` (int, entries < 0 = not forced): take this candidate instead of the argmin for those envs -
     used by the parity checker to follow a float32 run through an exact near-tie (``oracle/parity.py``).
@@ -464,7 +467,7 @@ def control_tick(cfg: OracleCfg, env: EnvBatch, cand, force_idx=None):
       4. upd_accum_obj   : ``accum += rho(obs, action) * sampling_time`` (controllers.py:1086-1093)
       5. ``step_idx += 1`` (int32)
     """
-    sim_substeps(cfg, env, cfg.substeps_per_tick)
+    (sim_substeps if sim is None else sim)(cfg, env, cfg.substeps_per_tick)
     if cfg.mode != MODE_MPC:
         # buffer push + critic refit every `critic_every_ticks` ticks (controllers.py:1458-1477)
         # critic_clock starts at t0 and tick j happens at t0 + (j + 1) dt, so `t - critic_clock >= critic_period`
@@ -1160,12 +1163,12 @@ def critic_fit_exact(A, b, w0, lo, hi, guess=None):
 
 
 def control_tick_opt(cfg: OracleCfg, env: EnvBatch, iters: int, warm_start: bool = False, action_init=None,
-                     memory=OPT_MEMORY):
+                     memory=OPT_MEMORY, sim=None):
     """``control_tick`` with :func:`actor_optimize` as the decision (twin of rcg_control_tick_opt): sim_step ->
     [RQL/SQL: buffer push + critic fit, as ``control_tick``] -> optimise from ``action_sqn_init`` (or, with
     ``warm_start`` after the first tick, from the previous optimum shifted by one step with the last step repeated) ->
-    action = first ``du`` entries -> accum, step_idx."""
-    sim_substeps(cfg, env, cfg.substeps_per_tick)
+    action = first ``du`` entries -> accum, step_idx.  ``sim``: the env step, as in :func:`control_tick`."""
+    (sim_substeps if sim is None else sim)(cfg, env, cfg.substeps_per_tick)
     if cfg.mode != MODE_MPC:
         every = max(int(cfg.critic_every_ticks), 1)
         critic_update(cfg, env, do_fit=((env.tick_count + 1) % every) == 0)
