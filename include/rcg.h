@@ -198,7 +198,7 @@ int rcg_device_count(void);
 /* A system of your own, compiled at run time for gfx950 (hipRTC) against the library's kernel headers.  `policy_src` is a
  * complete `struct <name> { ... };` in the shape of the built-ins ("Systems registered at run time"): DS, DU, NP,
  * template <typename real> struct Pre, prepare, rhs<real, HW>; optional jac_T (enables rcg_actor_optimize /
- * rcg_control_tick_opt), TGT, ZW_PRESET, SHARED_U1 (defaults false, 0, 0), and the output map (systems.py:185): DY
+ * rcg_control_tick_opt; or AUTODIFF, below, which derives it), TGT, ZW_PRESET, SHARED_U1 (defaults false, 0, 0), and the output map (systems.py:185): DY
  * (dim_output, default DS), out<real, HW>(q, x, y) (y = out(x); default y = x) and out_jac_T<real, HW>(q, x, gy, gx)
  * (gx = (d out / d x)^T gy; with out, rcg_actor_optimize needs it).  1 <= DY <= RCG_MAX_DS (RCG_ERR_UNSUPPORTED otherwise); a
  * DY other than DS without out is RCG_ERR_BAD_ARG.  With out every observation of the handle is [DY][B] (rcg_stage_obj,
@@ -258,7 +258,19 @@ int rcg_device_count(void);
  * rcg_episode_reset work as for them.  The rollouts of a decision stay disturbance-free, as in the reference.  The two kernels
  * are compiled as one program per element type the first time such a handle needs it, before the call enqueues anything; the
  * opt-in adds nothing to the registration itself.  RQL / SQL T ticks per launch, rcg_loop_step, the two-halves tick and the
- * nominal controllers are refused under the disturbance model, as for the built-in systems. */
+ * nominal controllers are refused under the disturbance model, as for the built-in systems.
+ * Derived adjoints: a policy opts in with `static constexpr bool AUTODIFF = true;` (optional, default false).  A member it does
+ * not write itself - jac_T, and out_jac_T when it has out - is then derived from rhs / out: the library instantiates them on a
+ * forward-mode dual number (rcg_dual.hpp: one value and DS + DU, or DS, tangents in registers) with the identity seeded on
+ * (x, u), and contracts the tangents with lam / gy - exact up to rounding, no finite differences.  A member the policy writes
+ * always wins; rcg_system_autodiff tells which were derived.  Everything that asks for jac_T then serves the policy as it serves
+ * one with hand-written members: rcg_actor_optimize, rcg_control_tick_opt, RCG_LOOP_DECIDE, rcg_jac_T.  Under the opt-in rhs
+ * and out must be written on `real` alone (no float / double locals) and may call, on real: + - * / and the compound
+ * assignments, comparisons, fma_r, sincos_sel, sincos_r, clamp_r, finite_r, sin, cos, tan, tanh, exp, log, sqrt, fabs, fmin,
+ * fmax, atan, atan2 and pow(x, constant exponent); any other function is a compile error (RCG_ERR_BAD_ARG with hipRTC's log).
+ * Pre<real> must be empty or hold members of type real only (arrays included): its fields are lifted one by one, and a
+ * static_assert that names Pre refuses anything else.  DS + DU <= 7 tangents (RCG_MAX_DS + RCG_MAX_DU).  A derived sweep costs
+ * more arithmetic than a hand-written one (DESIGN.md 13.8 has the measured ratio): jac_T stays the hand-tuned form. */
 int rcg_register_system(const char* name, const char* policy_src, int32_t ds, int32_t du, int32_t np, int32_t* sys_id);
 /* version of the runtime compiler rcg_register_system uses (hiprtcVersion) */
 int rcg_rtc_version(int32_t* major, int32_t* minor);
@@ -286,9 +298,14 @@ int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd);
  * with LOOP = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system and for yes == NULL.  (Added without a version
  * bump, RCG_VERSION: the symbol itself is how a caller detects that registered systems are served.) */
 int rcg_system_has_loop(int32_t sys_id, int32_t* yes);
+/* which adjoint members of a system were derived from rhs / out (a registered policy with AUTODIFF = true): bit 0 jac_T, bit 1
+ * out_jac_T; 0 for the built-in systems and for a policy that wrote its members or did not opt in.  RCG_ERR_BAD_ARG for an id
+ * that names no system and for mask == NULL.  (Added without a version bump, RCG_VERSION: the symbol itself is how a caller
+ * detects a library that derives them.) */
+int rcg_system_autodiff(int32_t sys_id, int32_t* mask);
 /* What has been compiled for a registered system so far, one line "<program>\t<name expression>\n" per kernel instance: the two
  * core programs of the registration, then whatever was compiled on first use (k_actor_dma instances, critic programs,
- * k_actor_search instances, k_ticks / k_ticks_mem instances, disturb programs, loop programs).  Writes at
+ * k_actor_search instances, k_ticks / k_ticks_mem instances, disturb programs, loop programs, k_jac_T of rcg_jac_T).  Writes at
  * most cap bytes (NUL-terminated) to buf and the size of the whole text, NUL included, to *need; buf or need may be NULL. */
 int rcg_system_programs(int32_t sys_id, char* buf, int64_t cap, int64_t* need);
 
@@ -351,6 +368,16 @@ int rcg_stage_obj(rcg_handle* h, const void* obs, const void* act, void* out, in
 /* System.out (systems.py:185): state [ds][n] -> obs [dy][n], in the handle's element type; the handle's per-env parameters
  * when n is its batch.  A system without an output map copies (dy = ds). */
 int rcg_out(rcg_handle* h, const void* state, void* obs, int32_t n);
+/* The adjoint products the optimiser's sweep takes of a system, in the form it takes them (rhs<real, true>'s trig), for n
+ * points: state [ds][n], action [du][n] (used as given, not clipped), lam [ds][n] -> ax [ds][n] = A^T lam, bu [du][n] = B^T lam
+ * with A = d rhs / d x, B = d rhs / d u; and gy [dy][n] -> gx [ds][n] = (d out / d x)^T gy (gy and gx both NULL: skipped; a
+ * system without an output map copies).  Parameters as in rcg_rhs.  The members are the policy's own or the derived ones
+ * (AUTODIFF): the way to check a hand-written jac_T against the derived one.  RCG_ERR_UNSUPPORTED naming the missing member,
+ * with the handle untouched, for a registered policy with neither the member nor AUTODIFF.  For a registered system the kernel
+ * is a program of its own, compiled the first time a handle of an element type asks for it (seconds), before anything is
+ * enqueued. */
+int rcg_jac_T(rcg_handle* h, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy,
+              void* gx, int32_t n);
 /* CtrlOptPred._critic (controllers.py:1192-1214): w [dc][n] -> out [n]. */
 int rcg_critic(rcg_handle* h, const void* obs, const void* act, const void* w, void* out, int32_t n);
 /* CtrlOptPred._actor_cost (controllers.py:1273-1328) for K candidate sequences per env.

@@ -55,8 +55,11 @@ SYMBOLS = [
     "rcg_actor_search", "rcg_control_tick_search", "rcg_candidates_sample", "rcg_release_stream",
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
     "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit", "rcg_last_launch_zero_w", "rcg_system_has_search",
-    "rcg_system_has_ticks", "rcg_system_disturb_dim", "rcg_system_has_loop",
+    "rcg_system_has_ticks", "rcg_system_disturb_dim", "rcg_system_has_loop", "rcg_system_autodiff",
 ]
+# (rcg_jac_T is bound in lib() like every other entry point; this list holds the names tests/test_abi.py can read out of rcg.h,
+# and its pattern takes lower-case names only)
+SYMBOLS_MIXED_CASE = ["rcg_jac_T"]
 KERNEL_ACTOR, KERNEL_SIM, KERNEL_CRITIC = 0, 1, 2
 # rcg_kernel_id (rcg_last_launch)
 (KID_NONE, KID_ACTOR, KID_ACTOR_DMA, KID_TICKS, KID_ACTOR_OPT, KID_NOMINAL, KID_SIM, KID_SIM_V, KID_SIM_DIST,
@@ -194,6 +197,8 @@ def lib():
         "rcg_system_has_ticks": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_system_disturb_dim": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_system_has_loop": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_system_autodiff": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_jac_T": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32]),
         "rcg_critic_fit": (C.c_int, [vp]),
         "rcg_system_programs": (C.c_int, [i32, C.c_char_p, i64, C.POINTER(i64)]),
     }
@@ -219,13 +224,14 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks", "dd", "has_loop"}``: the id to put in ``rcg_cfg.sys_id``
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks", "dd", "has_loop", "autodiff"}``: the id to put in ``rcg_cfg.sys_id``
     (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
     optimiser), its dim_output ``DY``, whether it defines the output map ``out`` and its adjoint ``out_jac_T``, and whether it opts
     in to the critic kernels (``CRITIC``: RQL / SQL), to the device search (``SEARCH``: rcg_actor_search) and to T ticks per launch
     (``TICKS``: rcg_control_ticks, the persistent path of rcg_control_tick_n), and ``dd``: its dim_disturb ``DD`` when it has the
     ``disturb`` member (the disturbance model: ``RCG_FLAG_DISTURB`` handles), else 0, and ``has_loop``: whether it opts in to the fused
-    loop step (``LOOP``: rcg_loop_step).  ``SYS_DIMS``
+    loop step (``LOOP``: rcg_loop_step), and ``autodiff``: which adjoint members were derived from ``rhs`` / ``out`` for a policy with
+    ``AUTODIFF`` (bit 0 ``jac_T``, bit 1 ``out_jac_T``; ``has_jac`` / ``has_out_jac`` count them as members).  ``SYS_DIMS``
     (``(ds, du, np)``), ``SYS_DY`` and - with ``disturb`` - ``DIM_DISTURB`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
     the dimension limits)."""
     import time
@@ -255,10 +261,12 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
         DIM_DISTURB[sid.value] = dd.value
     lp = C.c_int32(0)
     check(L.rcg_system_has_loop(sid.value, C.byref(lp)))
+    ad = C.c_int32(0)
+    check(L.rcg_system_autodiff(sid.value, C.byref(ad)))
     return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
             "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value),
             "has_critic": bool(crit.value), "has_search": bool(srch.value), "has_ticks": bool(tck.value), "dd": dd.value,
-            "has_loop": bool(lp.value)}
+            "has_loop": bool(lp.value), "autodiff": ad.value}
 
 
 def system_programs(sys_id: int) -> list:

@@ -90,7 +90,8 @@ class CtrlOptPred:
                 raise NotImplementedError(
                     f"{type(sys_obj).__name__} is compiled from hip_policy: the device search (actor_opt='sampling') needs the "
                     "policy to opt in with `static constexpr bool SEARCH = true;`, and the on-device optimiser needs jac_T in "
-                    "the policy (and out_jac_T with an output map out); add one of them or pass candidates=")
+                    "the policy (and out_jac_T with an output map out) - written by hand, or derived from rhs / out when the "
+                    "policy opts in with `static constexpr bool AUTODIFF = true;`; add one of them or pass candidates=")
             if actor_opt == "auto" and not has_opt and has_search:
                 actor_opt = "sampling"
         self.dim_input, self.dim_output = dim_input, dim_output

@@ -243,6 +243,14 @@ int rcg_system_has_loop(int32_t sys_id, int32_t* yes) {
   return RCG_OK;
 }
 
+int rcg_system_autodiff(int32_t sys_id, int32_t* mask) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_autodiff: bad sys_id %d", sys_id);
+  if (!mask) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_autodiff: null argument");
+  *mask = d.autodiff;
+  return RCG_OK;
+}
+
 int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd) {
   RtcDims d;
   if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_disturb_dim: bad sys_id %d", sys_id);
@@ -693,6 +701,14 @@ int rcg_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
   // no output map: the observation is the state (systems.py:185)
   HIPCHK(h, hipMemcpyAsync(obs, state, (size_t)h->ds * n * h->esz, hipMemcpyDeviceToDevice, h->stream));
   return RCG_OK;
+}
+
+int rcg_jac_T(rcg_handle* h, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy, void* gx,
+              int32_t n) {
+  DeviceGuard dev_guard(h);
+  if (!h || !state || !action || !lam || !ax || !bu || (gy == nullptr) != (gx == nullptr) || n < 1)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_jac_T: bad argument (gy and gx are given together or not at all)");
+  return h->sys->jac_T(h, state, action, lam, ax, bu, gy, gx, n);
 }
 
 int rcg_critic(rcg_handle* h, const void* obs, const void* act, const void* w, void* out, int32_t n) {

@@ -264,6 +264,9 @@ struct SysVTable {
   // rcg_loop_step's glue kernel (k_loop): [ACTION := act_in] -> [sim step] -> [stage cost + pack into `out`]; act_in / out: pinned host
   int (*loop)(rcg_handle*, const double* act_in, int32_t n_substeps, int32_t do_sim, int32_t do_tail, int32_t decided, int32_t dc,
               double* out, double* flag, double seq);
+  // rcg_jac_T: the adjoint products of the optimiser's sweep for n points (k_jac_T)
+  int (*jac_T)(rcg_handle*, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy, void* gx,
+               int32_t n);
 };
 extern const SysVTable kVt3WRobot, kVt3WRobotNI, kVt2Tank;
 
@@ -280,6 +283,7 @@ struct RtcDims {  // (`RtcDims d;` is the description of nothing)
   bool has_ticks = false;    // the policy opts in to T ticks per launch (static constexpr bool TICKS = true): k_ticks, k_ticks_mem
   int dd = 0;                // dim_disturb: the policy's DD when it has the `disturb` member (RCG_FLAG_DISTURB handles), else 0
   bool has_loop = false;     // the policy opts in to the fused loop step (static constexpr bool LOOP = true): rcg_loop_step
+  int autodiff = 0;          // the members derived from rhs / out (static constexpr bool AUTODIFF = true): bit 0 jac_T, bit 1 out_jac_T
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])

@@ -1346,6 +1346,43 @@ __global__ void k_out(const real* state, real* obs, const real* pars_env, long n
   for (int c = 0; c < DY; ++c) obs[(long)c * n + i] = y[c];
 }
 
+// The adjoint products of k_actor_opt's sweep for n points, lane == point (rcg_jac_T): (ax, bu) = (A^T lam, B^T lam) from
+// jac_T<real, true> and - gy given - gx = (d out / d x)^T gy from out_jac_T<real, true> (no output map: gx = gy), the members
+// as the sweep calls them; parameters as in k_rhs.  Instantiated only for a system that has the members.
+template <typename Sys, typename real>
+__global__ void k_jac_T(const real* state, const real* action, const real* lam, real* ax, real* bu, const real* gy, real* gx,
+                        const real* pars_env, long n, const KParams<real> P) {
+  constexpr int DS = Sys::DS, DU = Sys::DU, DY = sys_dy<Sys>();
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  real x[DS], u[DU], l[DS], a[DS], b[DU];
+#pragma unroll
+  for (int c = 0; c < DS; ++c) {
+    x[c] = state[(long)c * n + i];
+    l[c] = lam[(long)c * n + i];
+  }
+#pragma unroll
+  for (int c = 0; c < DU; ++c) u[c] = action[(long)c * n + i];
+  const auto pre = load_pre<Sys, real>(P, pars_env, i);
+  Sys::template jac_T<real, true>(pre, x, u, l, a, b);
+#pragma unroll
+  for (int c = 0; c < DS; ++c) ax[(long)c * n + i] = a[c];
+#pragma unroll
+  for (int c = 0; c < DU; ++c) bu[(long)c * n + i] = b[c];
+  if (!gy) return;
+  real g[DY], o[DS];
+#pragma unroll
+  for (int c = 0; c < DY; ++c) g[c] = gy[(long)c * n + i];
+  if constexpr (HasOut<Sys>::value) {
+    Sys::template out_jac_T<real, true>(pre, x, g, o);
+  } else {
+#pragma unroll
+    for (int c = 0; c < DS; ++c) o[c] = g[c];
+  }
+#pragma unroll
+  for (int c = 0; c < DS; ++c) gx[(long)c * n + i] = o[c];
+}
+
 template <typename Sys, typename real>
 __global__ void k_critic(const real* obs, const real* act, const real* w, real* out, long n, const KParams<real> P) {
   constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;  // the regressor is over [y - target, u]

@@ -83,9 +83,28 @@ __device__ __forceinline__ void sincos_fast(double x, double* s, double* c) {
   *c = ((k + 1) & 2) ? -cc : cc;
 }
 
+// Forward-mode dual numbers (rcg_dual.hpp; a policy registered at run time with AUTODIFF): only what the trig dispatch needs.
+// A dual's sine and cosine are dual_sincos<HW>: the value through sincos_sel<T, HW> of the value, so the HW selection below
+// still reaches the trig.  Nothing here names a dual for float / double: the built-in kernels compile as before.
+template <typename T>
+struct is_dual {
+  static constexpr bool value = false;
+};
+template <bool HW, typename D>
+__device__ __forceinline__ void dual_sincos(const D& x, D* s, D* c);
+
 template <typename real, bool HW>
 __device__ __forceinline__ void sincos_sel(real x, real* s, real* c) {
-  sincos_r<real>(x, s, c);
+  if constexpr (is_dual<real>::value)
+    dual_sincos<HW>(x, s, c);
+  else
+    sincos_r<real>(x, s, c);
+}
+// (the primary sincos_r: float and double are the specialisations above)
+template <typename real>
+__device__ __forceinline__ void sincos_r(real x, real* s, real* c) {
+  static_assert(is_dual<real>::value, "sincos_r: float, double or rcg::Dual of one");
+  dual_sincos<false>(x, s, c);
 }
 template <>
 __device__ __forceinline__ void sincos_sel<double, true>(double x, double* s, double* c) {

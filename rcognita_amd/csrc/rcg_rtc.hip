@@ -26,6 +26,11 @@
 //                    for a policy that opts in with `static constexpr bool LOOP = true`, the loop program of a handle's element
 //                    type and target setting, the first time the handle calls rcg_loop_step(_begin): k_loop and, when the policy
 //                    has jac_T (and out_jac_T with out), the LOOP instance of k_actor_opt (<name>_loop.hip);
+//                    for a policy with jac_T (and out_jac_T with out), k_jac_T of an element type the first time a handle calls
+//                    rcg_jac_T (<name>_jac.hip);
+//   A policy that opts in with `static constexpr bool AUTODIFF = true` has the adjoint members it does not write itself: the adapter
+//   derives jac_T / out_jac_T from rhs / out on forward-mode dual numbers (rcg_dual.hpp), the probe reports them as members, and
+//   everything above that asks for jac_T serves the policy as it serves one with hand-written members (rcg_system_autodiff).
 //   per device       a code object is loaded (hipModuleLoadData) the first time a handle on that device launches from it.
 // The grid, residency and LDS request of every decision launch come from actor_plan / opt_plan / search_plan / ticks_plan /
 // ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is
@@ -119,7 +124,7 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          (search ? "#include \"rcg_search.hpp\"\n" : "") +
          (ticks ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_ticks.hpp\"\n" : "") +
          (disturb ? "#include \"rcg_disturb.hpp\"\n" : "") +
-         "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
+         "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\n#include \"rcg_dual.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
          "namespace rtc {\n"
@@ -151,10 +156,31 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "template <class S> struct ddv { static constexpr int v = dist<S>::v ? (dd<S>::v == 0 ? -1 : dd<S>::v) : 0; };\n"
          "template <class S, class = void> struct lp { static constexpr bool v = false; };\n"
          "template <class S> struct lp<S, void_t<decltype(S::LOOP)>> { static constexpr bool v = S::LOOP; };\n"
-         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD, bool LP> "
-         "__global__ void k_rtc_probe() {}\n"
+         "template <class S, class = void> struct ad { static constexpr bool v = false; };\n"
+         "template <class S> struct ad<S, void_t<decltype(S::AUTODIFF)>> { static constexpr bool v = S::AUTODIFF; };\n"
+         // the adjoint members a policy with AUTODIFF does not write, derived from its rhs / out (rcg_dual.hpp); RcgRtcSys inherits
+         // them beside the policy, so a member the policy writes is the only one of its name
+         "template <class S, bool ON> struct ad_jac {};\n"
+         "template <class S> struct ad_jac<S, true> {\n"
+         "  template <typename real, bool HW = false>\n"
+         "  __device__ __forceinline__ static void jac_T(const typename S::template Pre<real>& q, const real* x, const real* u,\n"
+         "                                               const real* lam, real* ax, real* bu) {\n"
+         "    ad_jac_T<S, real, HW>(q, x, u, lam, ax, bu);\n"
+         "  }\n"
+         "};\n"
+         "template <class S, bool ON> struct ad_ojac {};\n"
+         "template <class S> struct ad_ojac<S, true> {\n"
+         "  template <typename real, bool HW = false>\n"
+         "  __device__ __forceinline__ static void out_jac_T(const typename S::template Pre<real>& q, const real* x, const real* gy,\n"
+         "                                                   real* gx) {\n"
+         "    ad_out_jac_T<S, real, HW, dy<S>::v>(q, x, gy, gx);\n"
+         "  }\n"
+         "};\n"
+         "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD, bool LP, "
+         "bool AD> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
-         "struct RcgRtcSys : " + N + " {\n"
+         "struct RcgRtcSys : " + N + ", rtc::ad_jac<" + N + ", rtc::ad<" + N + ">::v && !rtc::jac<" + N + ">::v>,\n"
+         "                   rtc::ad_ojac<" + N + ", rtc::ad<" + N + ">::v && rtc::out<" + N + ">::v && !rtc::ojac<" + N + ">::v> {\n"
          "  static constexpr bool TGT = rtc::tgt<" + N + ">::v;\n"
          "  static constexpr unsigned ZW_PRESET = rtc::zw<" + N + ">::v;\n"
          "  static constexpr unsigned SHARED_U1 = rtc::su1<" + N + ">::v;\n"
@@ -248,6 +274,10 @@ std::string expr_stage_obj() {
 template <typename real>
 std::string expr_out() {
   return std::string("rcg::k_out<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+template <typename real>
+std::string expr_jac_T() {
+  return std::string("rcg::k_jac_T<") + kSysExpr + ", " + real_name<real>() + ">";
 }
 template <typename real>
 std::string expr_sim(bool tgt) {
@@ -521,6 +551,37 @@ int rtc_rhs(rcg_handle* h, const void* state, const void* action, void* dstate, 
     int ci = clip;
     KParams<real> P = params<real>(h);
     void* args[] = {&st, &ac, &ds, &cl, &pe, &nn, &ci, &P};
+    return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+  });
+}
+
+// rcg_jac_T: k_jac_T of an element type, a program of its own compiled on first use (<name>_jac.hip; the registration compiles
+// what it compiled before) for a policy that has the members - its own or, AUTODIFF, the derived ones
+int rtc_jac_T(rcg_handle* h, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy, void* gx,
+              int32_t n) {
+  const RtcDims& d = h->rtc->dims;
+  if (!d.has_jac)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_jac_T: the policy %s defines no jac_T and does not opt in with AUTODIFF",
+                    h->rtc->name.c_str());
+  if (d.has_out && !d.has_out_jac)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_jac_T: the policy %s defines out but no out_jac_T and does not opt in with AUTODIFF",
+                    h->rtc->name.c_str());
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = lazy_function(h, Unit::Core, "jac", {expr_jac_T<real>()}, 0, &f);
+    if (rc) return rc;
+    const real* st = (const real*)state;
+    const real* ac = (const real*)action;
+    const real* la = (const real*)lam;
+    real* a = (real*)ax;
+    real* b = (real*)bu;
+    const real* g = (const real*)gy;
+    real* o = (real*)gx;
+    const real* pe = pars_env_of<real>(h, n);
+    long nn = n;
+    KParams<real> P = params<real>(h);
+    void* args[] = {&st, &ac, &la, &a, &b, &g, &o, &pe, &nn, &P};
     return launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
   });
 }
@@ -874,21 +935,21 @@ int rtc_loop(rcg_handle* h, const double* act_in, int32_t n_substeps, int32_t do
 }
 
 // the probe program: which optional members the policy has (the values travel in the lowered name of an empty kernel:
-// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW, DD, LP> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E;
-// DD: the policy's DD when it has `disturb`, else 0; LP: the policy's LOOP)
+// k_rtc_probe<TGT, JAC, DY, OUT, OJAC, CRIT, SRCH, TCK, ZW, DD, LP, AD> mangles its arguments as Lb0E / Lb1E, Li<n>E / Lin<n>E and Lj<n>E;
+// DD: the policy's DD when it has `disturb`, else 0; LP: the policy's LOOP; AD: its AUTODIFF)
 int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
-                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v, rcg::rtc::lp<" + pol + ">::v>";
+                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v, rcg::rtc::lp<" + pol + ">::v, rcg::rtc::ad<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S, Unit::Core), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[11];
+  long v[12];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 11 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 12 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -899,7 +960,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 11) {
+  if (n != 12) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -914,6 +975,11 @@ int probe(RtcSystem& S, std::string* log) {
   S.zw = (unsigned)v[8];
   S.dims.dd = (int)v[9];
   S.dims.has_loop = v[10] != 0;
+  // AUTODIFF: a member the policy does not write is derived (the adapter's mixins), and counts as one it has from here on
+  const bool ad = v[11] != 0;
+  S.dims.autodiff = (ad && !S.dims.has_jac ? 1 : 0) | (ad && S.dims.has_out && !S.dims.has_out_jac ? 2 : 0);
+  S.dims.has_jac = S.dims.has_jac || ad;
+  S.dims.has_out_jac = S.dims.has_out_jac || (S.dims.has_out && ad);
   return RCG_OK;
 }
 
@@ -922,7 +988,7 @@ int probe(RtcSystem& S, std::string* log) {
 #if !defined(__HIP_DEVICE_COMPILE__)  // (the table of host function pointers exists in the host pass only)
 const SysVTable kVtRtc = {&rtc_rhs,     &rtc_stage_obj, &rtc_critic,   &rtc_critic_cost, &rtc_actor,
                           &rtc_sim_step, &rtc_critic_update, &rtc_optimize, &rtc_nominal, &rtc_ticks,
-                          &rtc_rhs_full, &rtc_search,    &rtc_ticks_mem, &rtc_loop};
+                          &rtc_rhs_full, &rtc_search,    &rtc_ticks_mem, &rtc_loop, &rtc_jac_T};
 #endif
 
 int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {

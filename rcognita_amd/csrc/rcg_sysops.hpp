@@ -76,6 +76,19 @@ static int op_rhs(rcg_handle* h, const void* state, const void* action, void* ds
   });
 }
 
+// the adjoint products of the optimiser's sweep for n points (rcg_jac_T)
+template <typename Sys>
+static int op_jac_T(rcg_handle* h, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy,
+                    void* gx, int32_t n) {
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipLaunchKernelGGL((k_jac_T<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, h->stream, (const real*)state,
+                       (const real*)action, (const real*)lam, (real*)ax, (real*)bu, (const real*)gy, (real*)gx,
+                       pars_env_of<real>(h, n), (long)n, params<real>(h));
+    return launch_done(h);
+  });
+}
+
 static inline DisturbPars disturb_pars(const rcg_handle* h) {
   DisturbPars D;
   for (int k = 0; k < 2; ++k) {
@@ -1233,7 +1246,7 @@ struct SysInstances {
   static SysVTable table() {
     return SysVTable{&op_rhs<Sys>,   &op_stage_obj<Sys>, &op_critic<Sys>,        &op_critic_cost<Sys>, &op_actor<Sys>,
                      &op_sim_step<Sys>, &op_critic_update<Sys>, &op_optimize<Sys>, &op_nominal<Sys>,
-                     &op_ticks<Sys>,  &op_rhs_full<Sys>, &op_search<Sys>, &op_ticks_mem<Sys>, &op_loop<Sys>};
+                     &op_ticks<Sys>,  &op_rhs_full<Sys>, &op_search<Sys>, &op_ticks_mem<Sys>, &op_loop<Sys>, &op_jac_T<Sys>};
   }
 };
 

@@ -534,6 +534,27 @@ class Engine:
         N.check(N.lib().rcg_out(self._h, ps, C.c_void_p(y.ptr), n), self._h)
         return y.to_host().T.copy()
 
+    def jac_T(self, state, action, lam, gy=None):
+        """The adjoint products of the optimiser's sweep on ``n`` points (rcg_jac_T): ``state [n, ds]``, ``action [n, du]``,
+        ``lam [n, ds]`` -> ``(ax [n, ds], bu [n, du])`` = ``(A^T lam, B^T lam)``; with ``gy [n, dy]`` also
+        ``gx [n, ds] = (d out / d x)^T gy`` as a third entry.  The members are the policy's own or, with ``AUTODIFF``, the
+        derived ones; the trig is the rollouts' (``HW``)."""
+        state = np.asarray(state, dtype=self.real).reshape(-1, self.ds)
+        action = np.asarray(action, dtype=self.real).reshape(-1, self.du)
+        lam = np.asarray(lam, dtype=self.real).reshape(-1, self.ds)
+        n = state.shape[0]
+        keep = []
+        ps, pa, pl = (self._in(a, keep, lambda v: v.T) for a in (state, action, lam))
+        ax, bu = self._tmp((self.ds, n)), self._tmp((self.du, n))
+        pg = gx = None
+        if gy is not None:
+            pg = self._in(np.asarray(gy, dtype=self.real).reshape(-1, self.dy), keep, lambda v: v.T)
+            gx = self._tmp((self.ds, n))
+        N.check(N.lib().rcg_jac_T(self._h, ps, pa, pl, C.c_void_p(ax.ptr), C.c_void_p(bu.ptr), pg,
+                                  None if gx is None else C.c_void_p(gx.ptr), n), self._h)
+        res = (ax.to_host().T.copy(), bu.to_host().T.copy())
+        return res if gx is None else res + (gx.to_host().T.copy(),)
+
     def stage_obj(self, obs, act):
         obs = np.asarray(obs, dtype=self.real).reshape(-1, self.dy)
         act = np.asarray(act, dtype=self.real).reshape(-1, self.du)

@@ -23,9 +23,16 @@ The fused loop step (policies with LOOP): the first-use compil
 steps per second of the B = 1 drop-in loop (tools/b1_profile.py's bracket) for the pendulum (MPC), the pendulum with the output
 map (MPC, RQL) and a Sys2Tank copy next to the built-in Sys2Tank - fused, with Simulator.fuse = False and, when the root of
 another checkout with a built library is given, on that checkout (the parent commit), interleaved, medians of five.
+Derived adjoints (policies with AUTODIFF): the wall time of rcg_register_system for the pendulum and the corner
+system C2 (tests/user_systems.py: DS 5, DU 2, NP 5, DY 1 with out) with hand-written jac_T / out_jac_T and with the members
+derived; the k_actor_opt dispatch at B envs, Nactor, 5 iterations, 0 and 4 curvature pairs, f32 and f64, hand-written against
+derived, interleaved, medians of five from the dispatches' own stamps; and the registers and scratch of the two instances, read
+from an offline compile (hipcc -S, the library's options) of a unit that instantiates k_actor_opt for the policy as the runtime
+adapter does - the one part that needs no GPU (`autodiff-resources`).
 GPU box only; no torch.
 
-    python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks | disturb]      (search, ticks, disturb: that section alone)
+    python tools/user_system_probe.py [B] [K] [Nactor] [search | ticks | disturb | autodiff]      (that section alone)
+    python tools/user_system_probe.py 0 0 10 autodiff-resources
     python tools/user_system_probe.py 1 1 5 loop [root of another checkout]
 """
 import os
@@ -392,6 +399,120 @@ def loop_rows(other_root=None, steps=2000, rounds=5):
             w.wait(timeout=60)
 
 
+# ---- derived adjoints on policies with AUTODIFF ---------------------------------------------------------------
+def autodiff_policies():
+    """{case: (hand-written source, derived source, ds, du, np, pars, bnds, dy)}; the struct is named AdProbe<case><H|D>."""
+    from tests.user_systems import CORNERS, make_policy
+    from tests.user_systems_autodiff import autodiff_source
+
+    out = {}
+    hand = PENDULUM.replace("PendulumT", "AdProbePendH")
+    out["pendulum"] = (hand, autodiff_source(hand, "AdProbePendD"), 2, 1, 3, [1.3, 9.81, 0.7], np.array([[-5.0, 5.0]]), 2)
+    _, ds, du, np_, dy, dd = CORNERS["C2"]
+    src, twin = make_policy("AdProbeC2H", ds, du, np_, dy, 0)
+    out["C2"] = (src, autodiff_source(src, "AdProbeC2D"), ds, du, np_, twin.pars, twin.bnds, dy)
+    return out
+
+
+def autodiff_resources():
+    """VGPRs and private-segment bytes of k_actor_opt<.., TGT false, GENERIC g, PAIRS p> (and the LOOP instance) for each policy,
+    from `hipcc -S` of a unit shaped like the runtime compiler's: the kernel headers, the policy, an adapter struct that derives
+    from it and - derived variant - takes jac_T / out_jac_T from rcg_dual.hpp."""
+    import re
+    import subprocess
+    import tempfile
+
+    csrc = os.path.join(ROOT, "rcognita_amd", "csrc")
+    worst = 0
+    for case, (hand, derived, ds, du, np_, pars, bnds, dy) in autodiff_policies().items():
+        has_out = " static void out(" in hand
+        for tag, src in (("hand-written", hand), ("derived", derived)):
+            name = src[src.index("struct ") + 7:].split()[0]
+            mix = ""
+            if tag == "derived":
+                mix = ("  template <typename real, bool HW = false>\n"
+                       "  __device__ __forceinline__ static void jac_T(const typename P::template Pre<real>& q, const real* x, "
+                       "const real* u, const real* lam, real* ax, real* bu) { ad_jac_T<P, real, HW>(q, x, u, lam, ax, bu); }\n")
+                if has_out:
+                    mix += ("  template <typename real, bool HW = false>\n"
+                            "  __device__ __forceinline__ static void out_jac_T(const typename P::template Pre<real>& q, const real* x, "
+                            f"const real* gy, real* gx) {{ ad_out_jac_T<P, real, HW, {dy}>(q, x, gy, gx); }}\n")
+            inst = "".join(f"template __global__ void k_actor_opt<ProbeSys, {r}, false, {g}, {pr}{lp}>(const OptArgs<{r}>, const KParams<{r}>);\n"
+                           for r in ("float", "double") for g, pr, lp in (("false", "false", ""), ("true", "true", ""),
+                                                                          ("false", "false", ", true")))
+            unit = ('#include "rcg_actor_dma_packed.hpp"\n#include "rcg_actor_opt.hpp"\n#include "rcg_dual.hpp"\nnamespace rcg {\n' + src +
+                    f"struct ProbeSys : {name} {{\n  using P = {name};\n  static constexpr bool TGT = false;\n"
+                    "  static constexpr unsigned ZW_PRESET = 0u, SHARED_U1 = 0u;\n"
+                    f"  static constexpr bool HAS_OUT = {'true' if has_out else 'false'};\n  static constexpr int DY = {dy};\n" + mix +
+                    "};\n" + inst + "}\n")
+            with tempfile.TemporaryDirectory() as d:
+                f = os.path.join(d, "unit.hip")
+                open(f, "w").write(unit)
+                subprocess.check_call(["hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=fast", "--offload-device-only",
+                                       "-I" + csrc, "-I" + os.path.join(ROOT, "include"), "-S", f, "-o", os.path.join(d, "unit.s")])
+                asm = open(os.path.join(d, "unit.s")).read()
+            for meta in asm[asm.index("amdhsa.kernels:"):].split("\n  - ")[1:]:  # one entry per kernel, keys in alphabetical order
+                kern = re.search(r"\.name:\s+(\S+)", meta)
+                if kern is None or "k_actor_opt" not in kern.group(1):
+                    continue
+                kern = kern.group(1)
+                get = lambda k: int(re.search(r"\." + k + r":\s+(\d+)", meta).group(1))  # noqa: E731
+                real = "f64" if "ProbeSysEd" in kern else "f32"
+                flags = kern[kern.index("ProbeSysE") + 10:].split("EEv")[0]
+                form = {"Lb0ELb0ELb0ELb0E": "MPC diagonal (no pairs)", "Lb0ELb1ELb1ELb0E": "generic with pairs",
+                        "Lb0ELb0ELb0ELb1E": "LOOP (MPC diagonal)"}.get(flags, flags)
+                scratch = get("private_segment_fixed_size")
+                worst = max(worst, scratch if tag == "derived" else 0)
+                print(f"autodiff resources {case:9s} {tag:12s} {real} k_actor_opt {form:24s}: {get('vgpr_count')} VGPRs, "
+                      f"{get('sgpr_count')} SGPRs, private segment {scratch} B, LDS (static) {get('group_segment_fixed_size')} B")
+    print("autodiff resources: offline compile (hipcc -S) of the adapter-shaped unit; derived instances' largest private segment: "
+          f"{worst} B")
+
+
+def autodiff_rows(iters=5, reps=5):
+    rng = np.random.default_rng(5)
+    for case, (hand, derived, ds, du, np_, pars, bnds, dy) in autodiff_policies().items():
+        infos = {}
+        for tag, src in (("hand-written", hand), ("derived", derived)):
+            name = src[src.index("struct ") + 7:].split()[0]
+            infos[tag] = N.register_system(name, src, ds, du, np_)
+            print(f"autodiff {case:9s} {tag:12s}: rcg_register_system {infos[tag]['seconds']:.2f} s, autodiff mask {infos[tag]['autodiff']}")
+        assert infos["hand-written"]["autodiff"] == 0 and infos["derived"]["autodiff"] == (3 if infos["derived"]["has_out"] else 1)
+        x0 = rng.uniform(-2, 2, (B, ds))
+        for dtype in ("f32", "f64"):
+            for memory in (0, 4):
+                engines = []
+                for tag in ("hand-written", "derived"):
+                    e = Engine(EngineConfig(sys_id=infos[tag]["sys_id"], batch=B, dtype=dtype, Nactor=NH, pars=pars, ctrl_bnds=bnds,
+                                            R1=np.diag(np.linspace(10.0, 0.5, dy + du)), dt_sim=0.01, sampling_time=0.01, pred_step_size=0.02))
+                    e.set_state(x0)
+                    e.set_optimizer(memory)
+                    e.actor_optimize(iters)  # (warm-up: loads the code object)
+                    e.synchronize()
+                    e.profile([N.KERNEL_ACTOR])
+                    engines.append((tag, e))
+                for _ in range(reps):  # interleaved
+                    for tag, e in engines:
+                        e.actor_optimize(iters)
+                        e.synchronize()
+                med = {}
+                for tag, e in engines:
+                    t = e.profile_samples(N.KERNEL_ACTOR)
+                    med[tag] = float(np.median(t))
+                    ll = e.last_launch(N.KERNEL_ACTOR)
+                    print(f"autodiff {case:9s} {tag:12s} {dtype} memory {memory} {ll['kernel']}/{ll['variant']} at {B} envs, Nactor {NH}, "
+                          f"{iters} iterations: median of {len(t)} {med[tag]:.3f} ms (min {t.min():.3f} .. max {t.max():.3f})")
+                    e.close()
+                print(f"autodiff {case:9s} {dtype} memory {memory}: derived / hand-written = {med['derived'] / med['hand-written']:.3f}")
+
+
+if ONLY == "autodiff-resources":
+    autodiff_resources()
+    sys.exit(0)
+if ONLY == "autodiff":
+    autodiff_rows()
+    autodiff_resources()
+    sys.exit(0)
 if ONLY == "loop-worker":
     loop_worker()
     sys.exit(0)
