@@ -41,7 +41,7 @@ hdrs     = $(if $(wildcard $(1:.o=.d)),,$(ALLHDRS))
 # the kernel headers a runtime-compiled system needs, as string literals for rcg_rtc.hip (comments stripped)
 RTCHDRS := $(ROOT)include/rcg.h $(addprefix $(CSRC)/,rcg_math.hpp rcg_dual.hpp rcg_systems.hpp rcg_kernels.hpp rcg_loop.hpp rcg_actor_opt.hpp \
            rcg_actor_dma.hpp rcg_actor_dma_packed.hpp rcg_critic_fit.hpp rcg_critic_fit_ml.hpp rcg_critic_fit_gen.hpp \
-           rcg_disturb.hpp rcg_search.hpp rcg_ticks.hpp)
+           rcg_disturb.hpp rcg_search.hpp rcg_nominal.hpp rcg_ticks.hpp)
 # (the Makefile too: a header added to the list above must reach a library that was built before)
 $(GENDIR)/rcg_rtc_headers.inc: $(RTCHDRS) $(ROOT)tools/embed_rtc_headers.py $(ROOT)Makefile
 	@mkdir -p $(GENDIR)

@@ -209,10 +209,10 @@ int rcg_device_count(void);
  * (seconds; no device needed); a compile error is RCG_ERR_BAD_ARG with hipRTC's log in rcg_last_error(NULL).  The same name and
  * source again return the same id; the same name with another source is RCG_ERR_BAD_ARG.  There is no unregister.
  * A handle of such a system (rcg_cfg.sys_id = *sys_id) runs MPC: rcg_rhs, rcg_stage_obj, rcg_sim_step, rcg_actor_cost /
- * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  The nominal
- * controllers - and, without SEARCH (below), rcg_actor_search and rcg_control_tick_search, without TICKS (below)
- * rcg_control_ticks, without LOOP (below) rcg_loop_step, without the disturbance model (below) rcg_create with
- * RCG_FLAG_DISTURB - return RCG_ERR_UNSUPPORTED with the handle untouched.
+ * _argmin, rcg_control_tick (_n loops single ticks), rcg_actor_optimize and rcg_control_tick_opt (with jac_T).  Without the
+ * member `nominal` (below) the nominal controllers - and, without SEARCH (below), rcg_actor_search and
+ * rcg_control_tick_search, without TICKS (below) rcg_control_ticks, without LOOP (below) rcg_loop_step, without the disturbance
+ * model (below) rcg_create with RCG_FLAG_DISTURB - return RCG_ERR_UNSUPPORTED with the handle untouched.
  * RQL / SQL: a policy opts in with `static constexpr bool CRITIC = true;` (optional, default false).  Its handles then run every
  * mode and critic structure on the kernels the built-in systems run: rcg_critic, rcg_critic_cost, rcg_critic_update and the RQL /
  * SQL forms of rcg_actor_cost / _argmin, rcg_control_tick, rcg_actor_optimize and rcg_control_tick_opt.  The critic's regressor is
@@ -257,8 +257,28 @@ int rcg_device_count(void);
  * the kernels the built-in systems run; rcg_disturb_noise, RCG_FIELD_DISTURB ([DD][B]) / RCG_FIELD_SUBSTEP_IDX and
  * rcg_episode_reset work as for them.  The rollouts of a decision stay disturbance-free, as in the reference.  The two kernels
  * are compiled as one program per element type the first time such a handle needs it, before the call enqueues anything; the
- * opt-in adds nothing to the registration itself.  RQL / SQL T ticks per launch, rcg_loop_step, the two-halves tick and the
- * nominal controllers are refused under the disturbance model, as for the built-in systems.
+ * opt-in adds nothing to the registration itself.  RQL / SQL T ticks per launch, rcg_loop_step and the two-halves tick are
+ * refused under the disturbance model, as for the built-in systems; a nominal tick steps the env on k_sim_dist, as theirs does.
+ * The nominal control law (the reference's user writes a CtrlNominal... class beside the system): a policy
+ * opts in with the member `nominal`, beside rhs:
+ *   static constexpr int NOMINAL_NP = 2;   // optional, default 0: controller parameters after the gain, 0 .. 8
+ *   // the opt-in.  y: the observation, DY entries (DS without an output map); c[0] = ctrl_gain, c[1 .. NOMINAL_NP] = ctrl_pars;
+ *   // u: DU entries, unclipped
+ *   template <typename real>
+ *   __device__ __forceinline__ static void nominal(const Pre<real>& q, const real* y, const real* c, real* u);
+ *   // optional: compute_LF
+ *   template <typename real>
+ *   __device__ __forceinline__ static real nominal_lf(const Pre<real>& q, const real* y, const real* c);
+ * NOMINAL_NP outside 0 .. 8 is RCG_ERR_UNSUPPORTED; NOMINAL_NP or nominal_lf without nominal is RCG_ERR_BAD_ARG with a message
+ * that names the missing member.  The law is always evaluated in float64, whatever the handle's element type (the rule of the
+ * built-in laws): the members are instantiated on double only, Pre<double> comes from prepare<double> of the handle's parameters
+ * - the env's, with per-env parameters - widened, with an output map a tick takes y = out<double>(STATE), and an f32 handle
+ * returns the f64 law of its f32 values, rounded once.  rcg_nominal_action, rcg_control_tick_nominal and
+ * rcg_control_ticks_nominal then serve the system on k_nominal and - with TICKS as well - k_ticks_nominal, the kernels the
+ * built-in robots run; rcg_nominal_theta stays Sys3WRobot's.  The kernels are compiled as programs of their own the first time
+ * a handle needs them, before the call enqueues anything (a compile error is RCG_ERR_BAD_ARG with hipRTC's log in
+ * rcg_last_error and the handle untouched); the opt-in adds nothing to the registration itself.  Without the member the three
+ * entry points are RCG_ERR_UNSUPPORTED naming it, before anything is enqueued or any field moves.
  * Derived adjoints: a policy opts in with `static constexpr bool AUTODIFF = true;` (optional, default false).  A member it does
  * not write itself - jac_T, and out_jac_T when it has out - is then derived from rhs / out: the library instantiates them on a
  * forward-mode dual number (rcg_dual.hpp: one value and DS + DU, or DS, tangents in registers) with the identity seeded on
@@ -298,6 +318,14 @@ int rcg_system_disturb_dim(int32_t sys_id, int32_t* dd);
  * with LOOP = true, else 0.  RCG_ERR_BAD_ARG for an id that names no system and for yes == NULL.  (Added without a version
  * bump, RCG_VERSION: the symbol itself is how a caller detects that registered systems are served.) */
 int rcg_system_has_loop(int32_t sys_id, int32_t* yes);
+/* the nominal control law of a system (rcg_nominal_action, rcg_control_tick_nominal, rcg_control_ticks_nominal): bit 0 the law,
+ * bit 1 its Lyapunov function (compute_LF) - 3 for Sys3WRobot and Sys3WRobotNI, 0 for Sys2Tank, and for a registered policy
+ * bit 0 with the member `nominal`, bit 1 with `nominal_lf`.  RCG_ERR_BAD_ARG for an id that names no system and for
+ * mask == NULL.  (Added without a version bump, RCG_VERSION: the symbol itself tells a library that serves registered systems.) */
+int rcg_system_has_nominal(int32_t sys_id, int32_t* mask);
+/* how many controller parameters the law takes after the gain (ctrl_pars of the entry points): 2 for Sys3WRobot (m, I), a
+ * registered policy's NOMINAL_NP, else 0.  Argument errors as rcg_system_has_nominal. */
+int rcg_system_nominal_np(int32_t sys_id, int32_t* np);
 /* which adjoint members of a system were derived from rhs / out (a registered policy with AUTODIFF = true): bit 0 jac_T, bit 1
  * out_jac_T; 0 for the built-in systems and for a policy that wrote its members or did not opt in.  RCG_ERR_BAD_ARG for an id
  * that names no system and for mask == NULL.  (Added without a version bump, RCG_VERSION: the symbol itself is how a caller
@@ -584,7 +612,10 @@ int rcg_candidates_sample(rcg_handle* h, void* cand, int32_t K, int32_t round, c
  * compute_action does.  theta* of the 3wrobot controller (SciPy trust-constr in the reference) is build-defined:
  * a compass search from theta = 0 (step 0.25, halved whenever neither neighbour is lower, until 1e-9; round 6): the reference's
  * minimiser on 94.8 % of its fixture, Fc(theta*) never above the reference's (rounds 2-5: grid walk + golden section, 92.7 %).
- * Sys2Tank has no nominal controller: RCG_ERR_UNSUPPORTED. */
+ * Sys2Tank has no nominal controller: RCG_ERR_UNSUPPORTED.
+ * A registered system whose policy has the member `nominal` (rcg_register_system): obs is [DY][n], ctrl_pars points to
+ * NOMINAL_NP host doubles (NULL only when NOMINAL_NP == 0, else RCG_ERR_BAD_ARG), lyap needs `nominal_lf`
+ * (RCG_ERR_UNSUPPORTED naming it otherwise, nothing written), per-env parameters are taken as rcg_rhs takes them for n points. */
 int rcg_nominal_action(rcg_handle* h, const void* obs, void* action, void* lyap, int32_t n, double ctrl_gain,
                        const double* ctrl_pars, int32_t clip);
 /* theta* = argmin_theta Fc of CtrlNominal3WRobot._minimizer_theta (controllers.py:1618-1634; SciPy trust-constr there, the
@@ -593,8 +624,15 @@ int rcg_nominal_action(rcg_handle* h, const void* obs, void* action, void* lyap,
  * separately (the law is not Lipschitz in theta).  Sys3WRobot handles only. */
 int rcg_nominal_theta(rcg_handle* h, const void* obs, void* theta, int32_t n);
 /* One control tick under the nominal controller ('--ctrl_mode nominal', presets/main_3wrobot.py:425 through
- * ctrl_selector, controllers.py:58-59): sim_step -> ACTION := clipped nominal action of STATE -> ACCUM, STEP_IDX. */
+ * ctrl_selector, controllers.py:58-59): sim_step -> ACTION := clipped nominal action of STATE -> ACCUM, STEP_IDX.  A registered
+ * system with the member `nominal`: the law of out(STATE); under RCG_FLAG_DISTURB the env step is k_sim_dist, as for the robots. */
 int rcg_control_tick_nominal(rcg_handle* h, double ctrl_gain, const double* ctrl_pars);
+/* T consecutive rcg_control_tick_nominal.  ONE launch (k_ticks_nominal: lane = env, the env's fields in registers across the T
+ * ticks; rcg_last_launch reports RCG_KID_NOMINAL with variant bit 0 set) for Sys3WRobot, Sys3WRobotNI and a registered policy
+ * with `nominal` and TICKS; every field ends as T single ticks leave it, bit for bit, frozen envs included.  Everyone else with
+ * a law - a policy without TICKS, any handle with RCG_FLAG_DISTURB - gets the same T ticks issued as single ticks.  T < 1:
+ * RCG_ERR_BAD_ARG; Sys2Tank and a policy without `nominal`: RCG_ERR_UNSUPPORTED, nothing moved.  tick_count += T. */
+int rcg_control_ticks_nominal(rcg_handle* h, int32_t T, double ctrl_gain, const double* ctrl_pars);
 /* RQL/SQL bookkeeping of CtrlOptPred.compute_action (controllers.py:1458-1477): push (ACTION, obs)
  * into the buffers and, if do_fit != 0, refit W_CRITIC by bounded least squares on the TD stack of
  * _critic_cost (replacement of _critic_optimizer, controllers.py:1248-1271); W_PREV := W_CRITIC. */
@@ -649,7 +687,7 @@ typedef enum rcg_kernel_id {
   RCG_KID_ACTOR_DMA = 2,  /* k_actor_dma: the production streamed kernel (LDS-DMA tiles, unrolled register rollout)   */
   RCG_KID_TICKS = 3,      /* k_ticks: T ticks per launch (rcg_control_ticks)                                          */
   RCG_KID_ACTOR_OPT = 4,  /* k_actor_opt (rcg_actor_optimize / rcg_control_tick_opt)                                  */
-  RCG_KID_NOMINAL = 5,    /* k_nominal                                                                                */
+  RCG_KID_NOMINAL = 5,    /* k_nominal; variant bit 0: k_ticks_nominal, T nominal ticks per launch                    */
   RCG_KID_SIM = 6,        /* k_sim: lane = env                                                                        */
   RCG_KID_SIM_V = 7,      /* k_sim_v: lane = 16 bytes of consecutive envs                                             */
   RCG_KID_SIM_DIST = 8,   /* k_sim_dist: env step on the full state [state, disturb]                                  */

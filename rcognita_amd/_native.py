@@ -56,6 +56,7 @@ SYMBOLS = [
     "rcg_register_system", "rcg_rtc_version", "rcg_system_info", "rcg_system_output_info", "rcg_out",
     "rcg_system_has_critic", "rcg_system_programs", "rcg_critic_fit", "rcg_last_launch_zero_w", "rcg_system_has_search",
     "rcg_system_has_ticks", "rcg_system_disturb_dim", "rcg_system_has_loop", "rcg_system_autodiff",
+    "rcg_system_has_nominal", "rcg_system_nominal_np", "rcg_control_ticks_nominal",
 ]
 # (rcg_jac_T is bound in lib() like every other entry point; this list holds the names tests/test_abi.py can read out of rcg.h,
 # and its pattern takes lower-case names only)
@@ -173,6 +174,9 @@ def lib():
         "rcg_nominal_action": (C.c_int, [vp, vp, vp, vp, i32, C.c_double, C.POINTER(C.c_double), i32]),
         "rcg_control_tick_nominal": (C.c_int, [vp, C.c_double, C.POINTER(C.c_double)]),
         "rcg_nominal_theta": (C.c_int, [vp, vp, vp, i32]),
+        "rcg_control_ticks_nominal": (C.c_int, [vp, i32, C.c_double, C.POINTER(C.c_double)]),
+        "rcg_system_has_nominal": (C.c_int, [i32, C.POINTER(i32)]),
+        "rcg_system_nominal_np": (C.c_int, [i32, C.POINTER(i32)]),
         "rcg_rhs_full": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32]),
         "rcg_disturb_noise": (C.c_int, [vp, vp, vp]),
         "rcg_episode_reset": (C.c_int, [vp]),
@@ -224,14 +228,15 @@ def check(rc, handle=None, allow=()):
 
 def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     """Compile a system policy at run time (rcg_register_system, include/rcg.h) and return
-    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks", "dd", "has_loop", "autodiff"}``: the id to put in ``rcg_cfg.sys_id``
+    ``{"sys_id", "name", "seconds", "hiprtc", "has_jac", "dy", "has_out", "has_out_jac", "has_critic", "has_search", "has_ticks", "dd", "has_loop", "autodiff", "nominal", "nominal_np"}``: the id to put in ``rcg_cfg.sys_id``
     (>= SYS_USER_BASE), the wall time of the call, the runtime compiler's version, whether the policy has ``jac_T`` (the on-device
     optimiser), its dim_output ``DY``, whether it defines the output map ``out`` and its adjoint ``out_jac_T``, and whether it opts
     in to the critic kernels (``CRITIC``: RQL / SQL), to the device search (``SEARCH``: rcg_actor_search) and to T ticks per launch
     (``TICKS``: rcg_control_ticks, the persistent path of rcg_control_tick_n), and ``dd``: its dim_disturb ``DD`` when it has the
     ``disturb`` member (the disturbance model: ``RCG_FLAG_DISTURB`` handles), else 0, and ``has_loop``: whether it opts in to the fused
     loop step (``LOOP``: rcg_loop_step), and ``autodiff``: which adjoint members were derived from ``rhs`` / ``out`` for a policy with
-    ``AUTODIFF`` (bit 0 ``jac_T``, bit 1 ``out_jac_T``; ``has_jac`` / ``has_out_jac`` count them as members).  ``SYS_DIMS``
+    ``AUTODIFF`` (bit 0 ``jac_T``, bit 1 ``out_jac_T``; ``has_jac`` / ``has_out_jac`` count them as members), and ``nominal``: the
+    mask of rcg_system_has_nominal (bit 0 the member ``nominal``, bit 1 ``nominal_lf``) with ``nominal_np``, its ``NOMINAL_NP``.  ``SYS_DIMS``
     (``(ds, du, np)``), ``SYS_DY`` and - with ``disturb`` - ``DIM_DISTURB`` learn the new id.  Raises NativeError (BAD_ARG with the compiler's log, UNSUPPORTED beyond
     the dimension limits)."""
     import time
@@ -263,10 +268,13 @@ def register_system(name: str, src: str, ds: int, du: int, np: int) -> dict:
     check(L.rcg_system_has_loop(sid.value, C.byref(lp)))
     ad = C.c_int32(0)
     check(L.rcg_system_autodiff(sid.value, C.byref(ad)))
+    nom, nnp = C.c_int32(0), C.c_int32(0)
+    check(L.rcg_system_has_nominal(sid.value, C.byref(nom)))
+    check(L.rcg_system_nominal_np(sid.value, C.byref(nnp)))
     return {"sys_id": sid.value, "name": name, "seconds": seconds, "hiprtc": (a.value, b.value), "has_jac": bool(jac.value),
             "dy": dy.value, "has_out": bool(has_out.value), "has_out_jac": bool(has_out_jac.value),
             "has_critic": bool(crit.value), "has_search": bool(srch.value), "has_ticks": bool(tck.value), "dd": dd.value,
-            "has_loop": bool(lp.value), "autodiff": ad.value}
+            "has_loop": bool(lp.value), "autodiff": ad.value, "nominal": nom.value, "nominal_np": nnp.value}
 
 
 def system_programs(sys_id: int) -> list:

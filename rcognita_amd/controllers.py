@@ -620,3 +620,45 @@ class CtrlNominal3WRobotNI(_CtrlNominal):
 
     def __init__(self, ctrl_gain=10, ctrl_bnds=[], t0=0, sampling_time=0.1, dtype="f64", device=0):
         self._init(ctrl_gain, ctrl_bnds, t0, sampling_time, [], dtype, device)
+
+
+class CtrlNominal(_CtrlNominal):
+    """Nominal controller of a user's system: the counterpart of the ``CtrlNominal...`` class the reference's user writes beside
+    a system (rcognita/controllers.py:1495-1956 are its two examples).  The law is the ``nominal`` member of the system's
+    ``hip_policy`` (include/rcg.h), evaluated on the device in float64; ``ctrl_pars`` are its ``NOMINAL_NP`` parameters after the
+    gain.  ``compute_LF`` needs the member ``nominal_lf``.  Usable as ``ctrl_nominal`` of ``ctrl_selector(..., mode="nominal")``."""
+
+    def __init__(self, system, ctrl_gain, ctrl_pars=(), ctrl_bnds=[], t0=0, sampling_time=0.1, dtype="f64", device=0):
+        info = getattr(type(system), "_hip_info", None)
+        mask = info["nominal"] if info is not None else (0 if system._sys_id == N.SYS_2TANK else 3)
+        if not mask & 1:
+            raise NotImplementedError(f"{type(system).__name__}: its policy has no `nominal` member (the nominal control law, "
+                                      "include/rcg.h: rcg_register_system)")
+        self._system = system
+        self._sys_id, self._dy, self._du = system._sys_id, system.dim_output, system.dim_input
+        self._has_lf = bool(mask & 2)
+        self.ctrl_pars = [float(v) for v in ctrl_pars]
+        want = info["nominal_np"] if info is not None else None
+        if want is not None and len(self.ctrl_pars) != want:
+            raise ValueError(f"{type(system).__name__}: the nominal law takes {want} controller parameters (NOMINAL_NP), "
+                             f"got {len(self.ctrl_pars)}")
+        self._init(ctrl_gain, ctrl_bnds, t0, sampling_time, self.ctrl_pars, dtype, device)
+        self.ctrl_bnds = np.asarray(ctrl_bnds, dtype=float) if len(ctrl_bnds) else np.zeros((self._du, 2))
+        self.action_curr = np.zeros(self._du)
+
+    def _engine(self, n):
+        if self._eng is None or self._eng.B != n:
+            if self._eng is not None:
+                self._eng.close()
+            self._eng = Engine(EngineConfig(sys_id=self._sys_id, batch=n, dtype=self._dtype, device=self._device,
+                                            pars=list(self._system.pars), ctrl_bnds=self.ctrl_bnds if self.ctrl_bnds.any() else None))
+        return self._eng
+
+    def reset(self, t0):
+        self.ctrl_clock = t0
+        self.action_curr = np.zeros(self._du)
+
+    def compute_LF(self, observation):
+        if not self._has_lf:
+            raise NotImplementedError(f"{type(self._system).__name__}: its policy has no `nominal_lf` member")
+        return super().compute_LF(observation)

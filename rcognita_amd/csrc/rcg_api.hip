@@ -106,6 +106,8 @@ static bool system_dims(int sys_id, RtcDims* d, const RtcSystem** rtc = nullptr)
     d->np = kDims[sys_id][2];
     d->has_jac = d->has_critic = d->has_search = d->has_ticks = d->has_loop = true;
     d->dd = sys_id == RCG_SYS_2TANK ? 1 : 2;  // dim_disturb of the presets (main_*.py dim_disturb)
+    d->nominal = sys_id == RCG_SYS_2TANK ? 0 : 3;  // the two robots' laws and Lyapunov functions (rcg_nominal.hpp)
+    d->nominal_np = sys_id == RCG_SYS_3WROBOT ? 2 : 0;  // CtrlNominal3WRobot's (m, I)
     return true;
   }
   const RtcSystem* S = sys_id >= RCG_SYS_USER_BASE ? rtc_lookup(sys_id, d) : nullptr;
@@ -240,6 +242,22 @@ int rcg_system_has_loop(int32_t sys_id, int32_t* yes) {
   if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_loop: bad sys_id %d", sys_id);
   if (!yes) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_loop: null argument");
   *yes = d.has_loop ? 1 : 0;
+  return RCG_OK;
+}
+
+int rcg_system_has_nominal(int32_t sys_id, int32_t* mask) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_nominal: bad sys_id %d", sys_id);
+  if (!mask) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_has_nominal: null argument");
+  *mask = d.nominal;
+  return RCG_OK;
+}
+
+int rcg_system_nominal_np(int32_t sys_id, int32_t* np) {
+  RtcDims d;
+  if (!system_dims(sys_id, &d)) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_nominal_np: bad sys_id %d", sys_id);
+  if (!np) return rcg_fail(nullptr, RCG_ERR_BAD_ARG, "rcg_system_nominal_np: null argument");
+  *np = d.nominal_np;
   return RCG_OK;
 }
 
@@ -1304,6 +1322,10 @@ int rcg_nominal_action(rcg_handle* h, const void* obs, void* action, void* lyap,
   DeviceGuard dev_guard(h);
   if (!h || !obs || (!action && !lyap) || n < 1)
     return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_nominal_action: obs and one of action/lyap are required, n >= 1");
+  if (h->rtc) {  // the refusals, and the nominal program of the element type (compiled on first use), before anything is enqueued
+    const int rc = rtc_prepare_nominal(h, "rcg_nominal_action", lyap != nullptr, ctrl_pars, 0);
+    if (rc) return rc;
+  }
   return h->sys->nominal(h, obs, action, lyap, nullptr, n, ctrl_gain, ctrl_pars, clip, false);
 }
 
@@ -1320,14 +1342,42 @@ int rcg_control_tick_nominal(rcg_handle* h, double ctrl_gain, const double* ctrl
   if (!h) return RCG_ERR_BAD_ARG;
   if (h->cfg.sys_id == RCG_SYS_2TANK)  // refuse before the env is stepped
     return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_nominal: the reference defines no nominal controller for 2tank");
-  if (h->rtc)
-    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_tick_nominal: not available for a system registered at run time");
-  int rc = h->sys->sim_step(h, h->cfg.substeps_per_tick);
+  int rc = RCG_OK;
+  if (h->rtc) {  // a policy without `nominal` is refused by that name; the nominal program is resolved before the env is stepped
+    rc = rtc_prepare_nominal(h, "rcg_control_tick_nominal", false, ctrl_pars, 0);
+    if (rc) return rc;
+  }
+  rc = h->sys->sim_step(h, h->cfg.substeps_per_tick);
   if (rc) return rc;
   rc = h->sys->nominal(h, h->f[RCG_FIELD_STATE], h->f[RCG_FIELD_ACTION], nullptr, nullptr, h->cfg.batch, ctrl_gain,
                        ctrl_pars, 1, true);
   if (rc == RCG_OK) h->tick_count += 1;
   return rc;
+}
+
+int rcg_control_ticks_nominal(rcg_handle* h, int32_t T, double ctrl_gain, const double* ctrl_pars) {
+  DeviceGuard dev_guard(h);
+  if (!h) return RCG_ERR_BAD_ARG;
+  if (T < 1) return rcg_fail(h, RCG_ERR_BAD_ARG, "rcg_control_ticks_nominal: T must be >= 1");
+  if (h->cfg.sys_id == RCG_SYS_2TANK)
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "rcg_control_ticks_nominal: the reference defines no nominal controller for 2tank");
+  // one launch (k_ticks_nominal): the two robots, and a registered policy with `nominal` and TICKS; not under the disturbance
+  // model.  Everyone else with a law: the same T ticks as single ticks, as rcg_control_tick_n issues them
+  const bool persistent = !(h->cfg.flags & RCG_FLAG_DISTURB) && (!h->rtc || h->rtc_has_ticks);
+  if (h->rtc) {
+    const int rc = rtc_prepare_nominal(h, "rcg_control_ticks_nominal", false, ctrl_pars, persistent ? 2 : 1);
+    if (rc) return rc;
+  }
+  if (persistent) {
+    const int rc = h->sys->ticks_nominal(h, T, ctrl_gain, ctrl_pars);
+    if (rc == RCG_OK) h->tick_count += T;
+    return rc;
+  }
+  for (int32_t t = 0; t < T; ++t) {
+    const int rc = rcg_control_tick_nominal(h, ctrl_gain, ctrl_pars);
+    if (rc) return rc;
+  }
+  return RCG_OK;
 }
 
 int rcg_episode_reset(rcg_handle* h) {

@@ -267,6 +267,8 @@ struct SysVTable {
   // rcg_jac_T: the adjoint products of the optimiser's sweep for n points (k_jac_T)
   int (*jac_T)(rcg_handle*, const void* state, const void* action, const void* lam, void* ax, void* bu, const void* gy, void* gx,
                int32_t n);
+  // rcg_control_ticks_nominal: T nominal ticks in one launch (k_ticks_nominal); the caller has checked T, the system and the flags
+  int (*ticks_nominal)(rcg_handle*, int32_t T, double gain, const double* ctrl_pars);
 };
 extern const SysVTable kVt3WRobot, kVt3WRobotNI, kVt2Tank;
 
@@ -284,6 +286,8 @@ struct RtcDims {  // (`RtcDims d;` is the description of nothing)
   int dd = 0;                // dim_disturb: the policy's DD when it has the `disturb` member (RCG_FLAG_DISTURB handles), else 0
   bool has_loop = false;     // the policy opts in to the fused loop step (static constexpr bool LOOP = true): rcg_loop_step
   int autodiff = 0;          // the members derived from rhs / out (static constexpr bool AUTODIFF = true): bit 0 jac_T, bit 1 out_jac_T
+  int nominal = 0;           // the nominal control law: bit 0 the policy's `nominal` member (k_nominal, k_ticks_nominal), bit 1 `nominal_lf`
+  int nominal_np = 0;        // the policy's NOMINAL_NP (default 0): controller parameters after the gain, 0 .. RCG_NOMINAL_MAX_NP
 };
 const RtcSystem* rtc_lookup(int sys_id, RtcDims* dims);
 // rcg_out for a registered system with an output map: k_out (state [ds][n] -> obs [dy][n])
@@ -299,6 +303,11 @@ int rtc_prepare_tick_search(rcg_handle* h, int32_t K, int32_t rounds, int32_t wa
 // program of the handle (and, for a critic push, the critic program's fit kernel) resolved - compiled on first use - before the
 // step enqueues anything
 int rtc_loop_refusals(rcg_handle* h, bool decide);
+// rcg_nominal_action / rcg_control_tick_nominal / rcg_control_ticks_nominal on a registered system: refuses a policy without the
+// `nominal` member by that name, a Lyapunov value without `nominal_lf`, and missing ctrl_pars; then resolves - compiling on first
+// use - the nominal program of the element type, and for `ticks` > 0 the k_ticks_nominal instance (`ticks` > 1: a policy with
+// TICKS only), before the call enqueues anything
+int rtc_prepare_nominal(rcg_handle* h, const char* who, bool want_lyap, const double* ctrl_pars, int ticks);
 int rtc_prepare_loop(rcg_handle* h, bool push);
 extern const SysVTable kVtRtc;
 // sets the thread's error text (rcg_last_error(NULL)) without rcg_fail's length limit: hipRTC's log

@@ -16,6 +16,7 @@
 // handle returns the f64 law of its f32 states, rounded once.  Sys2Tank has no nominal controller in the reference:
 // unsupported.
 #pragma once
+#define RCG_NOMINAL_HPP 1
 #include "rcg_kernels.hpp"
 
 namespace rcg {
@@ -92,16 +93,22 @@ __device__ __forceinline__ real nom_Fc(const real* xn, const real* eta, real sq3
   return finite_r<real>(F) ? F : inf_r<real>();
 }
 
+// Nominal<Sys>: the law of a system.  Two shapes:
+//   the built-in robots  act<real>(x, gain, m, I, u, L, theta), written here;
+//   `policy`             a system registered at run time whose policy has the member `nominal` (rcg.h): rcg_rtc.hip's adapter
+//                        generates Nominal<RcgRtcSys> from the policy's members in every unit that includes this header -
+//                        law(q, y, c, u) and, `has_lf`, lf(q, y, c), on Pre<double>, with c[0] = ctrl_gain and c[1 .. NP] =
+//                        ctrl_pars.  Like the built-in laws it is evaluated in float64 whatever the handle's element type.
 template <typename Sys>
 struct Nominal {
-  static constexpr bool supported = false;
+  static constexpr bool supported = false, policy = false;
   template <typename real>
   __device__ static void act(const real*, real, real, real, real*, real*, real*) {}
 };
 
 template <>
 struct Nominal<Sys3WRobotNI> {
-  static constexpr bool supported = true;
+  static constexpr bool supported = true, policy = false;
   // compute_action_vanila (controllers.py:1937-1947) and compute_LF (:1949-1955)
   template <typename real>
   __device__ static void act(const real* x, real gain, real, real, real* u, real* L, real* th_out) {
@@ -134,7 +141,7 @@ struct Nominal<Sys3WRobotNI> {
 
 template <>
 struct Nominal<Sys3WRobot> {
-  static constexpr bool supported = true;
+  static constexpr bool supported = true, policy = false;
   // compute_action_vanila (controllers.py:1733-1748) with the build's theta search; L = Fc(theta*) (compute_LF)
   template <typename real>
   __device__ static void act(const real* x, real gain, real m, real I, real* u, real* L, real* th_out) {
@@ -180,9 +187,85 @@ struct Nominal<Sys3WRobot> {
   }
 };
 
+// ---- the law of a policy (Nominal<Sys>::policy), shared by k_nominal and k_ticks_nominal (rcg_ticks.hpp) --------------------
+constexpr int NOM_MAX_NP = 8;  // NOMINAL_NP of a policy: 0 .. 8 (rcg.h)
+
+// Pre<double> of env b: prepare<double> of the handle's parameters - the env's, with per-env parameters - widened
+template <typename Sys, typename real>
+__device__ __forceinline__ typename Sys::template Pre<double> load_pre_wide(const KParams<real>& P, const real* pars_env, long b) {
+  double pv[Sys::NP > 0 ? Sys::NP : 1];
+#pragma unroll
+  for (int i = 0; i < Sys::NP; ++i) pv[i] = (double)(pars_env ? pars_env[(long)i * P.B + b] : P.pars[i]);
+  return Sys::template prepare<double>(pv);
+}
+
+// u = the law of one env, clipped (`clip`) and rounded once to the handle's element type; *L = nominal_lf (`want_lf`, a policy
+// that has it), else 0.  `in`: the observation [DY] or - obs_x, a system with an output map: a tick - the state [DS], of which
+// y = out<double>(state) is taken.  The law's inputs and outputs are pinned (pin_value): what the compiler may contract inside the
+// member is then the same in every kernel that inlines it, and k_ticks_nominal's bits equal k_nominal's.
+template <typename Sys, typename real>
+__device__ __forceinline__ void nominal_policy(const KParams<real>& P, const typename Sys::template Pre<double>& q, const double* c,
+                                               const real* in, int obs_x, int clip, bool want_lf, real* u, double* L) {
+  constexpr int DS = Sys::DS, DU = Sys::DU, DY = sys_dy<Sys>();
+  double yd[DY], ud[DU];
+  bool from_state = false;
+  if constexpr (HasOut<Sys>::value) from_state = obs_x != 0;
+  if (from_state) {
+    if constexpr (HasOut<Sys>::value) {
+      double xd[DS];
+#pragma unroll
+      for (int k = 0; k < DS; ++k) xd[k] = (double)in[k];
+      Sys::template out<double, false>(q, xd, yd);
+    }
+  } else {
+#pragma unroll
+    for (int k = 0; k < DY; ++k) yd[k] = (double)in[k];
+  }
+#pragma unroll
+  for (int k = 0; k < DY; ++k) pin_value(yd[k]);
+#pragma unroll
+  for (int k = 0; k < DU; ++k) ud[k] = 0;
+  Nominal<Sys>::law(q, yd, c, ud);
+#pragma unroll
+  for (int k = 0; k < DU; ++k) {
+    pin_value(ud[k]);
+    if (clip && P.clip) ud[k] = clamp_r<double>(ud[k], (double)P.lo[k], (double)P.hi[k]);
+    u[k] = (real)ud[k];
+  }
+  *L = 0;
+  if constexpr (Nominal<Sys>::has_lf) {
+    if (want_lf) {
+      // on a pinned copy of y: the two members then share no subexpression, and the law's bits do not depend on whether the
+      // policy has nominal_lf or on whether the value is asked for (k_ticks_nominal never asks)
+      double yl[DY];
+#pragma unroll
+      for (int k = 0; k < DY; ++k) {
+        yl[k] = yd[k];
+        pin_value(yl[k]);
+      }
+      double v = Nominal<Sys>::lf(q, yl, c);
+      pin_value(v);
+      *L = v;
+    }
+  }
+}
+
+// upd_accum_obj (controllers.py:1086-1093) as k_nominal states it, at the observation y [DY] and the rounded action
+template <typename Sys, typename real>
+__device__ __forceinline__ real nominal_charge(const KParams<real>& P, const real* y, const real* u, real accum) {
+  constexpr int DY = sys_dy<Sys>(), DU = Sys::DU, NCHI = DY + DU;
+  real chi[NCHI];
+  if (P.has_target)
+    make_chi<DY, DU, true, real>(P, y, u, chi);
+  else
+    make_chi<DY, DU, false, real>(P, y, u, chi);
+  accum += stage_any<NCHI, real>(P, chi) * P.sampling_time;
+  return accum;
+}
+
 template <typename real>
 struct NomArgs {
-  const real* obs;    // [ds][n]
+  const real* obs;    // [ds][n]; a policy: [dy][n], or (obs_x) the state [ds][n]
   real* action;       // [du][n] out (or nullptr)
   real* lyap;         // [n] out: compute_LF (or nullptr)
   real* theta;        // [n] out: theta* of _minimizer_theta (or nullptr; 0 for the closed-form NI controller)
@@ -191,6 +274,10 @@ struct NomArgs {
   long n;
   double gain, m, I;
   int clip;
+  // a policy's law (Nominal<Sys>::policy)
+  int obs_x;                 // `obs` holds states: y = out(state) (a tick of a system with an output map)
+  const real* pars_env;      // [np][n] or nullptr
+  double c[NOM_MAX_NP + 1];  // ctrl_gain, ctrl_pars
 };
 
 template <typename Sys, typename real>
@@ -198,35 +285,58 @@ __global__ __launch_bounds__(256) void k_nominal(const NomArgs<real> A, const KP
   constexpr int DS = Sys::DS, DU = Sys::DU, NCHI = DS + DU;
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= A.n) return;
-  real x[DS], u[DU];
-  double xd[DS], ud[DU], L, th;
+  if constexpr (Nominal<Sys>::policy) {
+    constexpr int DY = sys_dy<Sys>();
+    int obs_x = 0;
+    if constexpr (HasOut<Sys>::value) obs_x = A.obs_x;
+    real in[sys_dxy<Sys>()], u[DU];
+    load_obs_raw<Sys, real>(A.obs, obs_x, A.n, i, in);
+    const auto qd = load_pre_wide<Sys, real>(P, A.pars_env, i);
+    double L;
+    nominal_policy<Sys, real>(P, qd, A.c, in, obs_x, A.clip, A.lyap != nullptr, u, &L);
+    if (A.action) {
 #pragma unroll
-  for (int c = 0; c < DS; ++c) {
-    x[c] = A.obs[(long)c * A.n + i];
-    xd[c] = (double)x[c];
-  }
-  Nominal<Sys>::template act<double>(xd, A.gain, A.m, A.I, ud, &L, &th);
+      for (int c = 0; c < DU; ++c) A.action[(long)c * A.n + i] = u[c];
+    }
+    if (A.lyap) A.lyap[i] = (real)L;
+    if (A.theta) A.theta[i] = (real)0;
+    if (A.accum) {  // at y = out(STATE) as every tick kernel forms it (obs_of_raw)
+      real y[DY];
+      obs_of_raw<Sys, real>(load_pre<Sys, real>(P, A.pars_env, i), obs_x, in, y);
+      A.accum[i] = nominal_charge<Sys, real>(P, y, u, A.accum[i]);
+    }
+    if (A.step_idx) A.step_idx[i] += 1;
+  } else {
+    real x[DS], u[DU];
+    double xd[DS], ud[DU], L, th;
 #pragma unroll
-  for (int c = 0; c < DU; ++c) {
-    // compute_action clips (controllers.py:1712-1714), compute_action_vanila does not
-    if (A.clip && P.clip) ud[c] = clamp_r<double>(ud[c], (double)P.lo[c], (double)P.hi[c]);
-    u[c] = (real)ud[c];
-  }
-  if (A.action) {
+    for (int c = 0; c < DS; ++c) {
+      x[c] = A.obs[(long)c * A.n + i];
+      xd[c] = (double)x[c];
+    }
+    Nominal<Sys>::template act<double>(xd, A.gain, A.m, A.I, ud, &L, &th);
 #pragma unroll
-    for (int c = 0; c < DU; ++c) A.action[(long)c * A.n + i] = u[c];
+    for (int c = 0; c < DU; ++c) {
+      // compute_action clips (controllers.py:1712-1714), compute_action_vanila does not
+      if (A.clip && P.clip) ud[c] = clamp_r<double>(ud[c], (double)P.lo[c], (double)P.hi[c]);
+      u[c] = (real)ud[c];
+    }
+    if (A.action) {
+#pragma unroll
+      for (int c = 0; c < DU; ++c) A.action[(long)c * A.n + i] = u[c];
+    }
+    if (A.lyap) A.lyap[i] = (real)L;
+    if (A.theta) A.theta[i] = (real)th;
+    if (A.accum) {  // upd_accum_obj (controllers.py:1086-1093)
+      real chi[NCHI];
+      if (P.has_target)
+        make_chi<DS, DU, true, real>(P, x, u, chi);
+      else
+        make_chi<DS, DU, false, real>(P, x, u, chi);
+      A.accum[i] += stage_any<NCHI, real>(P, chi) * P.sampling_time;
+    }
+    if (A.step_idx) A.step_idx[i] += 1;
   }
-  if (A.lyap) A.lyap[i] = (real)L;
-  if (A.theta) A.theta[i] = (real)th;
-  if (A.accum) {  // upd_accum_obj (controllers.py:1086-1093)
-    real chi[NCHI];
-    if (P.has_target)
-      make_chi<DS, DU, true, real>(P, x, u, chi);
-    else
-      make_chi<DS, DU, false, real>(P, x, u, chi);
-    A.accum[i] += stage_any<NCHI, real>(P, chi) * P.sampling_time;
-  }
-  if (A.step_idx) A.step_idx[i] += 1;
 }
 
 }  // namespace rcg

@@ -36,7 +36,9 @@
 // ticks_mem_plan (rcg_sysops.hpp), the functions the built-in launchers use, those of the critic update from fit_plan.  What is
 // not compiled is refused with RCG_ERR_UNSUPPORTED before anything is enqueued: the critic kernels of a policy without CRITIC
 // (rcg_create refuses RQL / SQL for it), the device search of a policy without SEARCH, T ticks per launch of a policy without
-// TICKS, rcg_loop_step of a policy without LOOP (and its decision without jac_T), the nominal controllers; rcg_create refuses
+// TICKS, rcg_loop_step of a policy without LOOP (and its decision without jac_T), the nominal controllers of a policy without
+// the member `nominal` (with it: k_nominal as <name>_nominal.hip per element type, and - with TICKS - the k_ticks_nominal
+// instance of a handle as <name>_ticks_nominal.hip, both compiled on first use); rcg_create refuses
 // the disturbance model for a policy without `disturb`, and under it RQL / SQL through k_ticks_mem, the two-halves tick and the
 // fused env step stay refused or unfused as for the built-in systems.  One mutex
 // guards the registry and every cache, the compiler runs outside it, and a handle keeps the functions it has resolved; nothing
@@ -102,7 +104,7 @@ bool is_identifier(const char* s) {
 // The generated unit: the kernel headers of its flavour (Core: the probe, the core programs and the k_actor_dma instances), the
 // policy (its own file name and line numbers in hipRTC's log), the adapter that supplies the optional members and the checks of
 // the declared dimensions.
-enum class Unit { Core, Critic, Search, Ticks, Disturb, Loop };  // (Loop: the Core unit's headers hold k_loop and k_actor_opt)
+enum class Unit { Core, Critic, Search, Ticks, Disturb, Loop, Nominal };  // (Loop: the Core unit's headers hold k_loop and k_actor_opt)
 std::string unit_source(const RtcSystem& S, Unit unit) {
   const bool critic = unit == Unit::Critic, search = unit == Unit::Search, ticks = unit == Unit::Ticks;
   const bool disturb = unit == Unit::Disturb;
@@ -120,11 +122,18 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
            S.dims.ds, S.name.c_str(), S.dims.du, S.name.c_str(), S.dims.np, S.name.c_str(), S.name.c_str(), S.name.c_str(),
            S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str(), S.name.c_str());
   const std::string& N = S.name;
+  // the nominal law's members come together (the DD / disturb rule): NOMINAL_NP or nominal_lf without nominal names what is missing
+  const std::string nom_rules =
+      "static_assert(!rtc::nomnp<" + N + ">::has || rtc::nom<" + N + ">::v, \"rcg_register_system: " + N +
+      " defines NOMINAL_NP but no nominal member (the nominal control law: template <typename real> static void nominal(q, y, c, u))\");\n"
+      "static_assert(!rtc::nomlf<" + N + ">::v || rtc::nom<" + N + ">::v, \"rcg_register_system: " + N +
+      " defines nominal_lf but no nominal member (the nominal control law: template <typename real> static void nominal(q, y, c, u))\");\n";
   return std::string(critic ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_critic_fit_gen.hpp\"\n" : "") +
          (search ? "#include \"rcg_search.hpp\"\n" : "") +
          (ticks ? "#include \"rcg_critic_fit_ml.hpp\"\n#include \"rcg_ticks.hpp\"\n" : "") +
          (disturb ? "#include \"rcg_disturb.hpp\"\n" : "") +
-         "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\n#include \"rcg_dual.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
+         // (rcg_nominal.hpp in every unit: a policy's `nominal` may call the library's own law functions, and its text is compiled in all)
+         "#include \"rcg_actor_dma_packed.hpp\"\n#include \"rcg_actor_opt.hpp\"\n#include \"rcg_dual.hpp\"\n#include \"rcg_nominal.hpp\"\nnamespace rcg {\n#line 1 \"" + N + ".policy\"\n" +
          S.src +
          "\n#line 1 \"rcg_rtc_adapter\"\n"
          "namespace rtc {\n"
@@ -158,6 +167,12 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "template <class S> struct lp<S, void_t<decltype(S::LOOP)>> { static constexpr bool v = S::LOOP; };\n"
          "template <class S, class = void> struct ad { static constexpr bool v = false; };\n"
          "template <class S> struct ad<S, void_t<decltype(S::AUTODIFF)>> { static constexpr bool v = S::AUTODIFF; };\n"
+         "template <class S, class = void> struct nom { static constexpr bool v = false; };\n"
+         "template <class S> struct nom<S, void_t<decltype(&S::template nominal<double>)>> { static constexpr bool v = true; };\n"
+         "template <class S, class = void> struct nomlf { static constexpr bool v = false; };\n"
+         "template <class S> struct nomlf<S, void_t<decltype(&S::template nominal_lf<double>)>> { static constexpr bool v = true; };\n"
+         "template <class S, class = void> struct nomnp { static constexpr bool has = false; static constexpr int v = 0; };\n"
+         "template <class S> struct nomnp<S, void_t<decltype(S::NOMINAL_NP)>> { static constexpr bool has = true; static constexpr int v = S::NOMINAL_NP; };\n"
          // the adjoint members a policy with AUTODIFF does not write, derived from its rhs / out (rcg_dual.hpp); RcgRtcSys inherits
          // them beside the policy, so a member the policy writes is the only one of its name
          "template <class S, bool ON> struct ad_jac {};\n"
@@ -177,7 +192,7 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "  }\n"
          "};\n"
          "template <bool TGT, bool JAC, int DY, bool OUT, bool OJAC, bool CRIT, bool SRCH, bool TCK, unsigned ZW, int DD, bool LP, "
-         "bool AD> __global__ void k_rtc_probe() {}\n"
+         "bool AD, int NOM, int NNP> __global__ void k_rtc_probe() {}\n"
          "}  // namespace rtc\n"
          "struct RcgRtcSys : " + N + ", rtc::ad_jac<" + N + ", rtc::ad<" + N + ">::v && !rtc::jac<" + N + ">::v>,\n"
          "                   rtc::ad_ojac<" + N + ", rtc::ad<" + N + ">::v && rtc::out<" + N + ">::v && !rtc::ojac<" + N + ">::v> {\n"
@@ -210,8 +225,30 @@ std::string unit_source(const RtcSystem& S, Unit unit) {
          "};\n"
          "}  // namespace rtc\n"
          "template <> struct Disturb<RcgRtcSys> : rtc::disturb_of<" + N + ", (rtc::ddv<" + N + ">::v > 0)> {};\n"
+         "#endif\n"
+         // Nominal<RcgRtcSys>, in every unit that includes rcg_nominal.hpp (the nominal program; rcg_ticks.hpp names it): the policy's
+         // `nominal` / `nominal_lf` on double, or - a policy without the member - an unsupported one that does nothing (the entry
+         // points refuse such a policy by name before anything is launched)
+         "#ifdef RCG_NOMINAL_HPP\n"
+         "namespace rtc {\n"
+         "template <class S, bool ON, bool LF> struct nominal_of {\n"
+         "  static constexpr bool supported = false, policy = true, has_lf = false;\n"
+         "  __device__ __forceinline__ static void law(const typename S::template Pre<double>&, const double*, const double*, double*) {}\n"
+         "};\n"
+         "template <class S, bool LF> struct nominal_of<S, true, LF> {\n"
+         "  static constexpr bool supported = true, policy = true, has_lf = LF;\n"
+         "  __device__ __forceinline__ static void law(const typename S::template Pre<double>& q, const double* y, const double* c,\n"
+         "                                             double* u) {\n"
+         "    S::template nominal<double>(q, y, c, u);\n"
+         "  }\n"
+         "  __device__ __forceinline__ static double lf(const typename S::template Pre<double>& q, const double* y, const double* c) {\n"
+         "    if constexpr (LF) return S::template nominal_lf<double>(q, y, c); else return 0.0;\n"
+         "  }\n"
+         "};\n"
+         "}  // namespace rtc\n"
+         "template <> struct Nominal<RcgRtcSys> : rtc::nominal_of<" + N + ", rtc::nom<" + N + ">::v, rtc::nomlf<" + N + ">::v> {};\n"
          "#endif\n" +
-         dims + "}  // namespace rcg\n";
+         dims + nom_rules + "}  // namespace rcg\n";
 }
 
 // Compile `src` and look up the lowered names of `exprs`.  Returns RCG_OK, or RCG_ERR_BAD_ARG with hipRTC's log in *log.
@@ -286,6 +323,14 @@ std::string expr_sim(bool tgt) {
 template <typename real>
 std::string expr_sim_dist(bool tgt) {
   return std::string("rcg::k_sim_dist<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ">";
+}
+template <typename real>
+std::string expr_nominal() {
+  return std::string("rcg::k_nominal<") + kSysExpr + ", " + real_name<real>() + ">";
+}
+template <typename real>
+std::string expr_ticks_nominal(bool tgt) {
+  return std::string("rcg::k_ticks_nominal<") + kSysExpr + ", " + real_name<real>() + ", " + tf(tgt) + ">";
 }
 template <typename real>
 std::string expr_rhs_full() {
@@ -813,8 +858,66 @@ int rtc_critic_update(rcg_handle* h, int32_t n_substeps, int32_t do_push, int32_
     return rc;
   });
 }
-int rtc_nominal(rcg_handle* h, const void*, void*, void*, void*, int32_t, double, const double*, int32_t, bool) {
-  return refuse(h, "the nominal controller");
+// The nominal law of a policy with the member `nominal`: k_nominal with the law behind Nominal<RcgRtcSys>, a program of its own per
+// element type compiled on first use (<name>_nominal.hip), and k_ticks_nominal, the instance of an (element type, target setting)
+// in the Ticks unit (<name>_ticks_nominal.hip).  The entry points have refused and resolved through rtc_prepare_nominal.
+template <typename real>
+int nominal_function(rcg_handle* h, hipFunction_t* fn) {
+  return lazy_function(h, Unit::Nominal, "nominal", {expr_nominal<real>()}, 0, fn);
+}
+int rtc_nominal(rcg_handle* h, const void* obs, void* action, void* lyap, void* theta, int32_t n, double gain, const double* ctrl_pars,
+                int32_t clip, bool tick) {
+  const RtcDims& d = h->rtc->dims;
+  if (!(d.nominal & 1)) return refuse_opt_in(h, "the nominal controller", "the member nominal");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    int rc = nominal_function<real>(h, &f);
+    if (rc) return rc;
+    const rcg_cfg& c = h->cfg;
+    NomArgs<real> A;
+    memset(&A, 0, sizeof A);
+    A.obs = (const real*)obs;
+    A.action = (real*)action;
+    A.lyap = (real*)lyap;
+    A.theta = (real*)theta;
+    A.accum = (tick && !(c.flags & RCG_FLAG_ACCUM_EVERY_SUBSTEP)) ? (real*)h->f[RCG_FIELD_ACCUM] : nullptr;
+    A.step_idx = tick ? (int32_t*)h->f[RCG_FIELD_STEP_IDX] : nullptr;
+    A.n = n;
+    A.gain = gain;
+    A.clip = clip;
+    A.obs_x = (tick && d.has_out) ? 1 : 0;  // a tick observes out(STATE)
+    A.pars_env = pars_env_of<real>(h, n);
+    A.c[0] = gain;
+    for (int i = 0; i < d.nominal_np; ++i) A.c[1 + i] = ctrl_pars[i];
+    KParams<real> P = params<real>(h);
+    ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+    void* args[] = {&A, &P};
+    rc = launch(h, f, dim3(blocks_for(n)), dim3(256), 0, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 0, 64);
+    return rc;
+  });
+}
+int rtc_ticks_nominal(rcg_handle* h, int32_t T, double gain, const double* ctrl_pars) {
+  const RtcDims& d = h->rtc->dims;
+  if (!(d.nominal & 1)) return refuse_opt_in(h, "rcg_control_ticks_nominal", "the member nominal");
+  if (!d.has_ticks) return refuse_opt_in(h, "rcg_control_ticks_nominal", "TICKS");
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    TicksNomArgs<real> A;
+    TicksNomPlan L;
+    ticks_nominal_plan<real>(h, T, gain, A, L);
+    for (int i = 0; i < d.nominal_np; ++i) A.c[1 + i] = ctrl_pars[i];
+    hipFunction_t f;
+    int rc = lazy_function(h, Unit::Ticks, "ticks_nominal", {expr_ticks_nominal<real>(L.tgt)}, 0, &f);
+    if (rc) return rc;
+    KParams<real> P = params<real>(h);
+    ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+    void* args[] = {&A, &P};
+    rc = launch(h, f, L.grid, L.block, 0, args);
+    if (rc == RCG_OK) note_launch(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 1, 64);
+    return rc;
+  });
 }
 // T ticks in one launch: op_ticks' / op_ticks_mem's plan (ticks_plan, ticks_mem_plan) on the program compiled for its instance -
 // except the shell written for one built-in system (k_ticks_pk).  The instance is resolved - and compiled, the first time -
@@ -941,15 +1044,16 @@ int probe(RtcSystem& S, std::string* log) {
   const std::string pol = "rcg::" + S.name;
   const std::string e = std::string("rcg::rtc::k_rtc_probe<") + kSysExpr + "::TGT, rcg::rtc::jac<" + pol + ">::v, " + kSysExpr +
                         "::DY, " + kSysExpr + "::HAS_OUT, rcg::rtc::ojac<" + pol + ">::v, rcg::rtc::crit<" + pol + ">::v, rcg::rtc::srch<" + pol +
-                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v, rcg::rtc::lp<" + pol + ">::v, rcg::rtc::ad<" + pol + ">::v>";
+                        ">::v, rcg::rtc::tck<" + pol + ">::v, " + kSysExpr + "::ZW_PRESET, rcg::rtc::ddv<" + pol + ">::v, rcg::rtc::lp<" + pol + ">::v, rcg::rtc::ad<" + pol + ">::v, (rcg::rtc::nom<" + pol +
+                        ">::v ? 1 : 0) | (rcg::rtc::nomlf<" + pol + ">::v ? 2 : 0), rcg::rtc::nomnp<" + pol + ">::v>";
   RtcProgram P;
   const int rc = compile(unit_source(S, Unit::Core), S.name + "_probe.hip", {e}, &P, log);
   if (rc) return rc;
   const std::string& low = P.lowered[e];
-  long v[12];
+  long v[14];
   size_t p = low.find("IL");
   int n = 0;
-  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 12 && p + 2 < low.size() && low[p] == 'L'; ++n) {
+  for (p = p == std::string::npos ? p : p + 1; p != std::string::npos && n < 14 && p + 2 < low.size() && low[p] == 'L'; ++n) {
     const char t = low[p + 1];
     size_t q = p + 2;
     const bool neg = t == 'i' && low[q] == 'n';
@@ -960,7 +1064,7 @@ int probe(RtcSystem& S, std::string* log) {
     v[n] = neg ? -x : x;
     p = q + 1;
   }
-  if (n != 12) {
+  if (n != 14) {
     *log = "cannot read the probe instance " + low;
     return RCG_ERR_HIP;
   }
@@ -980,6 +1084,8 @@ int probe(RtcSystem& S, std::string* log) {
   S.dims.autodiff = (ad && !S.dims.has_jac ? 1 : 0) | (ad && S.dims.has_out && !S.dims.has_out_jac ? 2 : 0);
   S.dims.has_jac = S.dims.has_jac || ad;
   S.dims.has_out_jac = S.dims.has_out_jac || (S.dims.has_out && ad);
+  S.dims.nominal = (int)v[12];
+  S.dims.nominal_np = (int)v[13];
   return RCG_OK;
 }
 
@@ -988,7 +1094,7 @@ int probe(RtcSystem& S, std::string* log) {
 #if !defined(__HIP_DEVICE_COMPILE__)  // (the table of host function pointers exists in the host pass only)
 const SysVTable kVtRtc = {&rtc_rhs,     &rtc_stage_obj, &rtc_critic,   &rtc_critic_cost, &rtc_actor,
                           &rtc_sim_step, &rtc_critic_update, &rtc_optimize, &rtc_nominal, &rtc_ticks,
-                          &rtc_rhs_full, &rtc_search,    &rtc_ticks_mem, &rtc_loop, &rtc_jac_T};
+                          &rtc_rhs_full, &rtc_search,    &rtc_ticks_mem, &rtc_loop, &rtc_jac_T, &rtc_ticks_nominal};
 #endif
 
 int rtc_out(rcg_handle* h, const void* state, void* obs, int32_t n) {
@@ -1062,6 +1168,24 @@ int rtc_prepare_tick_opt(rcg_handle* h) {
                     h->rtc->name.c_str(), d.has_out ? " / out_jac_T" : "");
   hipFunction_t fit;
   return critic_fit_function(h, &fit);
+}
+
+int rtc_prepare_nominal(rcg_handle* h, const char* who, bool want_lyap, const double* ctrl_pars, int ticks) {
+  const RtcDims& d = h->rtc->dims;
+  if (!(d.nominal & 1)) return refuse_opt_in(h, who, "the member nominal");
+  if (want_lyap && !(d.nominal & 2))
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "%s: the policy %s defines no nominal_lf (the Lyapunov function of its nominal law)", who,
+                    h->rtc->name.c_str());
+  if (d.nominal_np > 0 && !ctrl_pars)
+    return rcg_fail(h, RCG_ERR_BAD_ARG, "%s: ctrl_pars must point to the %d controller parameters of %s (NOMINAL_NP)", who,
+                    d.nominal_np, h->rtc->name.c_str());
+  return by_dtype(h, [&](auto r) {
+    using real = decltype(r);
+    hipFunction_t f;
+    if (ticks < 2) return nominal_function<real>(h, &f);
+    if (!d.has_ticks) return refuse_opt_in(h, who, "TICKS");
+    return lazy_function(h, Unit::Ticks, "ticks_nominal", {expr_ticks_nominal<real>((h->cfg.flags & RCG_FLAG_HAS_TARGET) != 0)}, 0, &f);
+  });
 }
 
 int rtc_loop_refusals(rcg_handle* h, bool decide) {
@@ -1141,6 +1265,10 @@ int rcg_register_system(const char* name, const char* policy_src, int32_t ds, in
   // dim_disturb: DisturbPars, rcg_cfg::pars_disturb / disturb_init and the two normals of a Philox draw are sized for 2
   if (rc == RCG_OK && (S->dims.dd < 0 || S->dims.dd > 2))
     return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::DD = %d beyond 1 .. 2", name, S->dims.dd);
+  // NOMINAL_NP: NomArgs::c / TicksNomArgs::c hold the gain and NOM_MAX_NP parameters
+  if (rc == RCG_OK && (S->dims.nominal_np < 0 || S->dims.nominal_np > NOM_MAX_NP))
+    return rcg_fail(nullptr, RCG_ERR_UNSUPPORTED, "rcg_register_system: %s::NOMINAL_NP = %d beyond 0 .. %d", name, S->dims.nominal_np,
+                    NOM_MAX_NP);
   const std::string unit = unit_source(*S, Unit::Core);
   if (rc == RCG_OK) rc = compile(unit, S->name + "_f32.hip", core_exprs<float>(S->dims), &S->core[0], &log);
   if (rc == RCG_OK) rc = compile(unit, S->name + "_f64.hip", core_exprs<double>(S->dims), &S->core[1], &log);

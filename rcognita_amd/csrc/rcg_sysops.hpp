@@ -1230,9 +1230,62 @@ static int op_nominal(rcg_handle* h, const void* obs, void* action, void* lyap, 
       A.m = ctrl_pars ? ctrl_pars[0] : c.pars[0];
       A.I = ctrl_pars ? ctrl_pars[1] : c.pars[1];
       A.clip = clip;
+      A.obs_x = 0;  // (the three below: a registered policy's law, rcg_rtc.hip)
+      A.pars_env = nullptr;
+      memset(A.c, 0, sizeof A.c);
       ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
       RCG_LAUNCH(h, (k_nominal<Sys, real>), dim3(blocks_for(n)), dim3(256), 0, A, params<real>(h));
       return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 0, 64);
+    });
+  }
+}
+
+// k_ticks_nominal's arguments and launch shape for the handle - shared by the built-in robots' launcher below and rcg_rtc.hip.
+// Lane = env; up to 16 384 envs 64-lane blocks, so that the waves spread over the CUs (256 envs are four waves on four CUs
+// instead of one block on one), beyond that 256-lane blocks as k_sim / k_nominal.
+struct TicksNomPlan {
+  bool tgt;  // the instance: k_ticks_nominal<Sys, real, tgt>
+  dim3 grid, block;
+};
+template <typename real>
+static void ticks_nominal_plan(const rcg_handle* h, int32_t T, double gain, TicksNomArgs<real>& A, TicksNomPlan& L) {
+  const rcg_cfg& c = h->cfg;
+  memset(&A, 0, sizeof A);
+  A.state = (real*)h->f[RCG_FIELD_STATE];
+  A.state_prev = (real*)h->f[RCG_FIELD_STATE_PREV];
+  A.action = (real*)h->f[RCG_FIELD_ACTION];
+  A.pars_env = (const real*)h->f[RCG_FIELD_PARS];
+  A.accum = (real*)h->f[RCG_FIELD_ACCUM];
+  A.step_idx = (int32_t*)h->f[RCG_FIELD_STEP_IDX];
+  A.status = (uint32_t*)h->f[RCG_FIELD_STATUS];
+  A.T = T;
+  A.n_sub = c.substeps_per_tick;
+  A.gain = gain;
+  A.c[0] = gain;
+  L.tgt = (c.flags & RCG_FLAG_HAS_TARGET) != 0;
+  const int bs = c.batch <= 16384 ? 64 : 256;
+  L.grid = dim3(blocks_for(c.batch, bs));
+  L.block = dim3(bs);
+}
+
+// rcg_control_ticks_nominal for the two robots: T nominal ticks in one launch (k_ticks_nominal).  The caller has checked T, the
+// system and the flags (no disturbance model).
+template <typename Sys>
+static int op_ticks_nominal(rcg_handle* h, int32_t T, double gain, const double* ctrl_pars) {
+  if constexpr (!Nominal<Sys>::supported) {
+    return rcg_fail(h, RCG_ERR_UNSUPPORTED, "nominal controller: the reference defines none for this system");
+  } else {
+    const rcg_cfg& c = h->cfg;
+    return by_dtype(h, [&](auto r) {
+      using real = decltype(r);
+      TicksNomArgs<real> A;
+      TicksNomPlan L;
+      ticks_nominal_plan<real>(h, T, gain, A, L);
+      A.m = ctrl_pars ? ctrl_pars[0] : c.pars[0];  // as op_nominal
+      A.I = ctrl_pars ? ctrl_pars[1] : c.pars[1];
+      ProfScope prof_scope(h, RCG_KERNEL_ACTOR);
+      with_bools([&](auto TGT) { RCG_LAUNCH(h, (k_ticks_nominal<Sys, real, TGT()>), L.grid, L.block, 0, A, params<real>(h)); }, L.tgt);
+      return launch_done(h, RCG_KERNEL_ACTOR, RCG_KID_NOMINAL, 1, 64);
     });
   }
 }
@@ -1246,7 +1299,8 @@ struct SysInstances {
   static SysVTable table() {
     return SysVTable{&op_rhs<Sys>,   &op_stage_obj<Sys>, &op_critic<Sys>,        &op_critic_cost<Sys>, &op_actor<Sys>,
                      &op_sim_step<Sys>, &op_critic_update<Sys>, &op_optimize<Sys>, &op_nominal<Sys>,
-                     &op_ticks<Sys>,  &op_rhs_full<Sys>, &op_search<Sys>, &op_ticks_mem<Sys>, &op_loop<Sys>, &op_jac_T<Sys>};
+                     &op_ticks<Sys>,  &op_rhs_full<Sys>, &op_search<Sys>, &op_ticks_mem<Sys>, &op_loop<Sys>, &op_jac_T<Sys>,
+                     &op_ticks_nominal<Sys>};
   }
 };
 

@@ -20,6 +20,7 @@
 #include "rcg_critic_fit.hpp"
 #include "rcg_disturb.hpp"
 #include "rcg_kernels.hpp"
+#include "rcg_nominal.hpp"
 
 namespace rcg {
 
@@ -346,6 +347,107 @@ __global__ __launch_bounds__(256) void k_ticks_mem(const TicksMemArgs<real> M, c
   } else {
     if (lane < envs_here) critic_ring_unrotate<Sys, real>(F, P, wave * G + lane, M.T);
   }
+}
+
+// ---------------------------------------------------------------------------------------------
+// k_ticks_nominal: T nominal ticks in ONE launch (rcg_control_ticks_nominal)
+// ---------------------------------------------------------------------------------------------
+// A nominal tick is k_sim* then k_nominal - two launches for about a microsecond of work per wave - and an env's tick depends
+// on nothing but that env.  Lane = env: the env's state, previous state, held action, accum, step counter and status are loaded
+// once (struct of arrays: coalesced), live in registers across the T ticks and are stored once.  A tick runs env_substeps (the
+// function k_sim inlines) and the law (Nominal<Sys>::act<double>, or nominal_policy for a registered policy - the functions
+// k_nominal inlines) with k_nominal's statements for the clip and the stage cost, so every field ends as T calls of
+// rcg_control_tick_nominal leave it, bit for bit - a frozen env included: env_substeps does not step it, the law still decides
+// for it, it is counted and charged.  No LDS, no barrier, no batch limit.  (The disturbance model stays on single ticks.)
+template <typename real>
+struct TicksNomArgs {
+  real* state;           // [ds][B] in/out
+  real* state_prev;      // [ds][B] in/out
+  real* action;          // [du][B] in/out: the held action (ZOH)
+  const real* pars_env;  // [np][B] or nullptr
+  real* accum;           // [B] in/out
+  int32_t* step_idx;     // [B] in/out
+  uint32_t* status;      // [B] in/out
+  int T;                 // ticks
+  int n_sub;             // RK4 substeps per tick
+  double gain, m, I;         // the built-in laws (NomArgs)
+  double c[NOM_MAX_NP + 1];  // a policy's law: ctrl_gain, ctrl_pars
+};
+
+template <typename Sys, typename real, bool TGT>
+__global__ __launch_bounds__(256) void k_ticks_nominal(const TicksNomArgs<real> A, const KParams<real> P) {
+  constexpr int DS = Sys::DS, DU = Sys::DU;
+  const long B = P.B;
+  const long b = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  real x[DS], xp[DS], u[DU];
+#pragma unroll
+  for (int c = 0; c < DS; ++c) {
+    x[c] = A.state[(long)c * B + b];
+    xp[c] = A.state_prev[(long)c * B + b];
+  }
+#pragma unroll
+  for (int c = 0; c < DU; ++c) u[c] = A.action[(long)c * B + b];
+  const auto pre = load_pre<Sys, real>(P, A.pars_env, b);
+  uint32_t st = A.status[b];
+  real accum = A.accum[b];
+  int32_t steps = A.step_idx[b];
+
+  for (int t = 0; t < A.T; ++t) {
+    env_substeps<Sys, real, TGT>(P, pre, A.n_sub, x, xp, u, st, accum);  // k_sim
+    // k_nominal on STATE (clip = 1)
+    if constexpr (Nominal<Sys>::policy) {
+      constexpr int DY = sys_dy<Sys>(), DXY = sys_dxy<Sys>();
+      constexpr int obs_x = HasOut<Sys>::value ? 1 : 0;
+      real in[DXY];
+#pragma unroll
+      for (int c = 0; c < DXY; ++c) in[c] = c < DS ? x[c < DS ? c : 0] : (real)0;
+      const auto qd = load_pre_wide<Sys, real>(P, A.pars_env, b);
+      double L;
+      nominal_policy<Sys, real>(P, qd, A.c, in, obs_x, 1, false, u, &L);
+      if (!P.accum_every_substep) {
+        real y[DY];
+        obs_of_raw<Sys, real>(pre, obs_x, in, y);
+        accum = nominal_charge<Sys, real>(P, y, u, accum);
+      }
+    } else {
+      constexpr int NCHI = DS + DU;
+      double xd[DS], ud[DU], L, th;
+#pragma unroll
+      for (int c = 0; c < DS; ++c) {
+        xd[c] = (double)x[c];
+        pin_value(xd[c]);  // a value of its own, as k_nominal's load is: the law contracts as it does there
+      }
+      Nominal<Sys>::template act<double>(xd, A.gain, A.m, A.I, ud, &L, &th);
+      asm volatile("" ::"v"(L), "v"(th));  // (k_nominal computes both: kept alive, so that shared subexpressions have the same users)
+#pragma unroll
+      for (int c = 0; c < DU; ++c) {
+        pin_value(ud[c]);
+        if (P.clip) ud[c] = clamp_r<double>(ud[c], (double)P.lo[c], (double)P.hi[c]);
+        u[c] = (real)ud[c];
+      }
+      if (!P.accum_every_substep) {  // upd_accum_obj: k_nominal's statements
+        real chi[NCHI];
+        if (P.has_target)
+          make_chi<DS, DU, true, real>(P, x, u, chi);
+        else
+          make_chi<DS, DU, false, real>(P, x, u, chi);
+        accum += stage_any<NCHI, real>(P, chi) * P.sampling_time;
+      }
+    }
+    steps += 1;
+  }
+
+#pragma unroll
+  for (int c = 0; c < DS; ++c) {
+    A.state[(long)c * B + b] = x[c];
+    A.state_prev[(long)c * B + b] = xp[c];
+  }
+#pragma unroll
+  for (int c = 0; c < DU; ++c) A.action[(long)c * B + b] = u[c];
+  A.accum[b] = accum;
+  A.step_idx[b] = steps;
+  A.status[b] = st;
 }
 
 }  // namespace rcg

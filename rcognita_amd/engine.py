@@ -795,10 +795,13 @@ class Engine:
 
     @staticmethod
     def _ctrl_pars(ctrl_pars):
+        """Host doubles of a nominal law's parameters: (m, I) of CtrlNominal3WRobot, the NOMINAL_NP values of a policy's law."""
         if ctrl_pars is None:
             return None
-        m, I = (float(v) for v in ctrl_pars)
-        return (C.c_double * 2)(m, I)
+        vals = [float(v) for v in ctrl_pars]
+        if not vals:
+            return None
+        return (C.c_double * len(vals))(*vals)
 
     def nominal_action(self, obs, ctrl_gain, ctrl_pars=None, clip=False, want_lyap=False):
         """Nominal controller of the handle's system on ``obs [n, dy]`` (rcg_nominal_action): returns ``action [n, du]``
@@ -822,9 +825,15 @@ class Engine:
         N.check(N.lib().rcg_nominal_theta(self._h, self._in(obs, keep, lambda a: a.T), pth, n), self._h)
         return fetch()[0]
 
-    def control_tick_nominal(self, ctrl_gain, ctrl_pars=None):
-        """One env.control-step with the nominal controller as the decision (rcg_control_tick_nominal)."""
-        N.check(N.lib().rcg_control_tick_nominal(self._h, float(ctrl_gain), self._ctrl_pars(ctrl_pars)), self._h)
+    def control_tick_nominal(self, ctrl_gain, ctrl_pars=None, T=1):
+        """``T`` env.control-steps with the nominal controller as the decision.  ``T = 1``: the single tick it always was
+        (rcg_control_tick_nominal: k_sim* then k_nominal); ``T > 1``: rcg_control_ticks_nominal - one launch (k_ticks_nominal) for
+        the two robots and a policy with ``nominal`` and ``TICKS``, else the same ticks issued natively - with every field as
+        ``T`` single ticks leave it, bit for bit."""
+        if int(T) == 1:
+            N.check(N.lib().rcg_control_tick_nominal(self._h, float(ctrl_gain), self._ctrl_pars(ctrl_pars)), self._h)
+        else:
+            N.check(N.lib().rcg_control_ticks_nominal(self._h, int(T), float(ctrl_gain), self._ctrl_pars(ctrl_pars)), self._h)
 
     def critic_update(self, do_fit=True):
         N.check(N.lib().rcg_critic_update(self._h, 1 if do_fit else 0), self._h)

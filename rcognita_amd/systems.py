@@ -100,6 +100,8 @@ class System:
             if e.code == N.ERR_BAD_ARG and "differs from the declared" in str(e):
                 raise ValueError(f"{cls.__name__}: the dimensions (state, input, pars) = {tuple(dims)} do not match the struct "
                                  f"{m.group(1)}: {e}") from None
+            if e.code == N.ERR_BAD_ARG and "but no nominal member" in str(e):  # NOMINAL_NP / nominal_lf without the law itself
+                raise ValueError(f"{cls.__name__}: the nominal control law of {m.group(1)} is incomplete: {e}") from None
             raise
         cls._hip_info = info
         cls._sys_id = info["sys_id"]
